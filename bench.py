@@ -17,14 +17,19 @@ shape of ``cml_raw_example.nc``) windowed with T = 181. Every timed step is a fu
 training step: on-device window gather, forward, weighted BCE, backward, gradient
 all-reduce (N > 1), Adam update.
 
-After the timed region the same line carries the quality half of BASELINE.json's headline metric
+A plain run does only that: set up, warm up, time ``--steps`` steps, write the outputs of the last
+timed batches if ``--dump-outputs DIR`` is given (computed from the seeded weights so that runs compare,
+:func:`dump_outputs`), print the line. ``--full`` adds the side records:
+after the timed region the same line then carries the same measurement on the k=5 graph (``knn5``)
+and the quality half of BASELINE.json's headline metric
 ("ROC-AUC (5-fold CV)"): the paper's 5-fold CV of the CML GCN and of the graph-less baseline LSTM
 (``cv``; folds dealt over the ranks under --gpus N, CML data in which only the neighbourhood tells
 rain-shaped anomalies from rain), the integrated-gradients throughput (``ig``), and the second dataset
 of the headline (``soilnet``: SoilNet GCN training throughput, B=32 x T=337, same timed-step
 contract, and its 5-fold CV against the baseline on the generator with neighbour-only faults).
-``--no-cv-line`` / ``--no-ig-line`` / ``--no-soil-line`` skip them. ``--time-layer cnn`` measures the
-CNN TimeLayer branch instead (diagnostic line, no side records).
+Under ``--full``, ``--no-knn-line`` / ``--no-cv-line`` / ``--no-ig-line`` / ``--no-soil-line`` skip
+single records. ``--time-layer cnn`` measures the CNN TimeLayer branch instead (diagnostic line, no
+side records).
 
 Prints ONE JSON line on rank 0.
 """
@@ -299,9 +304,10 @@ def train_data(args, ds: str, sensors: int, days: int):
     return pc, mc, create_windows_dataset(pc, raw=raw)
 
 
-def measure_train(args, ds, pc, mc, ws, graph_cfg, batch, dev, world, rank, D, baseline=False):
+def measure_train(args, ds, pc, mc, ws, graph_cfg, batch, dev, world, rank, D, baseline=False, dump_dir=None):
     """Build store / model / trainer for one dataset and adjacency rule, warm up, time args.steps full
-    training steps (max over ranks). Returns (seconds, trainer, loss, trainable params)."""
+    training steps (max over ranks), then write :func:`dump_outputs` to ``dump_dir`` if one is given. Returns
+    (seconds, trainer, loss of the last timed step, trainable params)."""
     from gnnqc.data.store import DeviceLoader, DeviceStore
     from gnnqc.models import BaselineClassifier, GCNClassifier
     from gnnqc.ops.optim import make_optimizer
@@ -321,6 +327,7 @@ def measure_train(args, ds, pc, mc, ws, graph_cfg, batch, dev, world, rank, D, b
     # every one of the steps is a full training step (gather, forward, backward, guarded Adam); chunks of
     # trainer.graph_steps of them replay one multi-step HIP graph
     trainer.prepare_graphs(rows)              # graph captures happen here, never inside the timed steps
+    seeded = _train_state(trainer) if dump_dir else None
     trainer.train_steps(rows, 0, args.warmup)
     trainer._comm_events = []
     D.barrier()
@@ -332,7 +339,77 @@ def measure_train(args, ds, pc, mc, ws, graph_cfg, batch, dev, world, rank, D, b
         torch.cuda.synchronize()
     D.barrier()
     dt = D.max_over_ranks(time.perf_counter() - t0)
-    return dt, trainer, float(trainer.last_loss.item()), n_params
+    loss = float(trainer.last_loss.item())    # (read before the dump's step: graph replays refresh the tensor)
+    if dump_dir:
+        dump_outputs(dump_dir, trainer, rows, args.warmup, args.steps, seeded, rank)
+    return dt, trainer, loss, n_params
+
+
+def _train_state(trainer):
+    """Model state_dict, optimizer state and step count as copies (``FlatAdam.state_dict`` hands out
+    its live moment tensors when they already are on the CPU)."""
+    opt = {k: v.detach().clone() if torch.is_tensor(v) else v for k, v in trainer.opt.state_dict().items()}
+    return {k: v.detach().clone() for k, v in trainer.model.state_dict().items()}, opt, trainer.global_step
+
+
+def _set_train_state(trainer, state):
+    weights, opt, step = state
+    with torch.no_grad():
+        for k, v in trainer.model.state_dict().items():
+            v.copy_(weights[k])
+    trainer.opt.load_state_dict(opt)
+    trainer.opt.zero_grad()
+    trainer.global_step = step
+
+
+def _dump_steps(trainer, n_timed):
+    """Steps that :func:`dump_outputs` runs from the seeded state: one chunk of the multi-step graph when
+    the timed steps replayed it, else one step."""
+    S = trainer.graph_steps
+    return S if trainer.multi_graph is not None and trainer._multi_ok() and n_timed >= S else 1
+
+
+def dump_outputs(path, trainer, rows, warmup, steps, seeded, rank):
+    """``--dump-outputs``: ``path/<name>.npy`` (float32 / float64, about 3 MB), written after the timed
+    region on rank 0.
+
+    ``timed_steps.npy`` says what the timed steps did: [steps attempted, steps the guard applied, steps it
+    rejected, batch cursor of the multi-step graph] after warm-up + timed steps (exact counts).
+
+    Everything else is what the timed path (``Trainer.train_steps`` with the graphs captured for the timed
+    steps: one chunk of the multi-step graph where the timed steps replayed it, else one step) computes
+    for the LAST timed batches from the SEEDED initial weights and zero optimizer state ``seeded``:
+    ``loss.npy`` (the loss it returns), every entry of the model's ``state_dict`` as it leaves it, and
+    Adam's moments ``optimizer.m.npy`` / ``optimizer.v.npy`` (flat, parameter order), which carry the
+    gradients' magnitudes where the first updates themselves are close to lr * sign(g).
+
+    Not dumped: the weights the timed steps end on. They are not a function of the inputs alone: the
+    store-fused GCN backward adds its parameter gradients with float atomics, and Adam carries that
+    last-bit noise into weights that differ in the fourth digit after 25 steps (measured: up to 1.7e-4,
+    0.8 % of an array's largest value) and without bound after thousands, so two runs of one build do not
+    compare on them. A few steps from the seeded state agree from run to run to rounding (measured on one
+    MI355X, one 8-step chunk, three runs: some 60 of the 188k moment elements, two GCN arrays and once a
+    single LSTM weight differ at all, by at most 2e-9 absolute, 1e-7 of their array's largest value; the
+    other arrays are bitwise equal). The loss the
+    timed steps end on is the line's ``final_loss``. The trainer is put back to where the timed steps left
+    it (the ``--full`` records measure on it)."""
+    import numpy as np
+    end = _train_state(trainer)
+    counts = [end[1]["iterations"], end[1]["step"], end[1]["skipped_steps"], int(trainer._cursor.item())]
+    k = min(_dump_steps(trainer, steps), warmup + steps)
+    _set_train_state(trainer, seeded)
+    loss = float(trainer.train_steps(rows, warmup + steps - k, k).item())
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        out = {"timed_steps": np.asarray(counts, dtype=np.float64), "loss": np.asarray([loss], dtype=np.float64)}
+        for name, t in trainer.model.state_dict().items():
+            t = t.detach()
+            out[name] = t.float().cpu().numpy() if t.is_floating_point() else t.cpu().numpy().astype(np.float64)
+        for name in ("m", "v"):
+            out["optimizer." + name] = getattr(trainer.opt, name).detach().float().cpu().numpy()
+        for name, a in out.items():
+            np.save(os.path.join(path, name + ".npy"), a)
+    _set_train_state(trainer, end)
 
 
 def _release(dev):
@@ -357,6 +434,14 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the side records of the headline line (knn5, ig, cv, "
+                         "soilnet; under --gpus N the standalone timing of an in-graph all-reduce); a plain run "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/<name>.npy (float32 / float64, rank 0): the timed steps' "
+                         "step counts, and what the timed path computes for the last timed batches from the seeded "
+                         "initial weights - loss, model parameters and buffers, Adam moments (see dump_outputs)")
     ap.add_argument("--batch", type=int, default=None, help="windows per GPU per step (default: config batch_size,"
                     " CML 128 / SoilNet 32)")
     ap.add_argument("--model", choices=["gcn", "baseline"], default="gcn")
@@ -440,11 +525,11 @@ def main(argv=None):
                 f"radius(max_sample_distance={pc.graph['max_sample_distance']})")
 
     dt, trainer, loss, n_params = measure_train(args, args.ds, pc, mc, ws, pc.graph, args.batch, dev, world, rank, D,
-                                                baseline)
+                                                baseline, dump_dir=args.dump_outputs)
     comm_us = None
     if trainer._comm_events:             # N > 1, eager layout: HIP events around the timed all-reduces
         comm_us = 1e3 * sum(a.elapsed_time(b) for a, b in trainer._comm_events) / len(trainer._comm_events)
-    elif trainer.collective:             # in-graph all-reduce: the same collective timed on its own, after
+    elif trainer.collective and args.full:   # in-graph all-reduce: the same collective timed on its own, after
         comm_us = trainer.measure_allreduce()
     if comm_us is not None:
         comm_us = D.max_over_ranks(comm_us)
@@ -453,7 +538,7 @@ def main(argv=None):
     dp_graph = trainer.dp_graph and trainer._multi_ok()
     windows = args.steps * args.batch * world
     value = windows / dt
-    side = not soil and not cnn            # the side records ride on the headline (CML, LSTM) line
+    side = args.full and not soil and not cnn   # the side records ride on the headline (CML, LSTM) line
     knn = ig = cv = soil_rec = None
     if side and args.knn_line and args.adjacency == "radius":
         # BASELINE.json names the CML graph "k=5": the same measurement on the symmetrised

@@ -14,7 +14,7 @@ for r in $(seq 1 ${RUNS:-2}); do
       echo "soil $name run $r: $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/envab_soil_${name}_$r.log | head -1)" | tee -a $OUT
     fi
     if [ "${IG:-1}" = 1 ]; then
-      env $kv timeout -k 10 200 python3 bench.py --steps 8 --warmup 2 --no-knn-line --no-cv-line --no-soil-line \
+      env $kv timeout -k 10 200 python3 bench.py --steps 8 --warmup 2 --full --no-knn-line --no-cv-line --no-soil-line \
           > gpurun_out/envab_ig_${name}_$r.log 2>&1 || exit 3
       echo "ig $name run $r: $(grep -o '"ms_per_call": [0-9.]*' gpurun_out/envab_ig_${name}_$r.log)" | tee -a $OUT
     fi

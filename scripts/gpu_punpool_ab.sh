@@ -10,7 +10,7 @@ timeout -k 10 500 python -u -m pytest -x -v --timeout 120 --timeout-method threa
   && VARIANTS="${VARIANTS:-pu1:- pu0:GNNQC_CHAINB_PUNPOOL=0}" bash scripts/gpu_prof_variants.sh \
   && for r in 1 2; do
     for v in 1 0; do
-      GNNQC_CHAINB_PUNPOOL=$v timeout -k 10 200 python -u bench.py --gpus 1 --steps 20 --warmup 5 \
+      GNNQC_CHAINB_PUNPOOL=$v timeout -k 10 200 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full \
         > gpurun_out/bench_pu${v}_$r.log 2>&1 || exit 3
       echo "pu$v run $r: $(grep -m1 '"metric"' gpurun_out/bench_pu${v}_$r.log)"
     done

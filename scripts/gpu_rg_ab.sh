@@ -10,7 +10,7 @@ for r in 1 2; do
     GNNQC_TM_RG=$v timeout -k 10 200 python3 bench.py --ds soilnet --steps 40 --warmup 8 --no-knn-line \
         > gpurun_out/rgab_soil_${v}_$r.log 2>&1 || exit 3
     echo "soil RG=$v run $r: $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/rgab_soil_${v}_$r.log)" | tee -a $OUT
-    GNNQC_TM_RG=$v timeout -k 10 200 python3 bench.py --steps 8 --warmup 2 --no-knn-line --no-cv-line --no-soil-line \
+    GNNQC_TM_RG=$v timeout -k 10 200 python3 bench.py --steps 8 --warmup 2 --full --no-knn-line --no-cv-line --no-soil-line \
         > gpurun_out/rgab_ig_${v}_$r.log 2>&1 || exit 3
     echo "ig RG=$v run $r: $(grep -o '"ms_per_call": [0-9.]*' gpurun_out/rgab_ig_${v}_$r.log)" | tee -a $OUT
   done

@@ -36,8 +36,8 @@ for step in "$@"; do
     case $step in
         tests)  run tests 600 $PY -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider ;;
         smoke)  run smoke 300 $PY -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench)  run bench 300 $PY bench.py --steps 50 --warmup 10 ;;
-        bench1) run bench1 600 $PY bench.py --gpus 1 --steps 20 --warmup 5 ;;
+        bench)  run bench 300 $PY bench.py --steps 50 --warmup 10 --full ;;
+        bench1) run bench1 600 $PY bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
         soil)   run soil 300 $PY bench.py --ds soilnet --steps 20 --warmup 5 --no-knn-line ;;
         cnn)    run cnn 300 $PY bench.py --time-layer cnn --steps 40 --warmup 5 ;;
         stats_cnn) prof stats_cnn 400 --kernel-trace --stats -d "$OUT/prof_stats_cnn" -o run --output-format csv -- \
@@ -48,8 +48,8 @@ for step in "$@"; do
                     --output-format csv -- $PY "$ROOT/bench.py" --time-layer cnn --steps 16 --warmup 2 ;;
         pmc_cnn_wr) prof pmc_cnn_wr 120 --kernel-trace --pmc WRITE_SIZE -d "$OUT/prof_pmc_cnn_wr" -o run \
                     --output-format csv -- $PY "$ROOT/bench.py" --time-layer cnn --steps 16 --warmup 2 ;;
-        cvcml)  run cvcml 400 $PY bench.py --steps 8 --warmup 2 --no-knn-line --no-ig-line --no-soil-line ${CV_ARGS:-} ;;
-        cvsoil) run cvsoil 600 $PY bench.py --steps 8 --warmup 2 --no-knn-line --no-ig-line ${CV_ARGS:-} ;;
+        cvcml)  run cvcml 400 $PY bench.py --steps 8 --warmup 2 --full --no-knn-line --no-ig-line --no-soil-line ${CV_ARGS:-} ;;
+        cvsoil) run cvsoil 600 $PY bench.py --steps 8 --warmup 2 --full --no-knn-line --no-ig-line ${CV_ARGS:-} ;;
         ig)     run ig 300 $PY scripts/bench_ig.py ;;
         ar)     run ar 300 $PY scripts/ar_us.py ;;
         phase)  GNNQC_HIP_LIB=gnnqc/_lib/variants/prof.so run phase 300 $PY scripts/chain_phase_prof.py ;;

@@ -13,9 +13,30 @@ from gnnqc.ckpt.tensorbundle import bundle_entries, read_bundle, read_sstable, w
 from gnnqc.models import create_model
 from gnnqc.ops.optim import FlatAdam
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_ckpt")
 REF_MODELS = ["model_cml", "model_cml_baseline", "model_soilnet", "model_soilnet_baseline"]
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "model_cml")), reason="reference checkpoints absent")
+DATA = "variables.data-00000-of-00001"
+
+
+@pytest.fixture(scope="session")
+def REF(tmp_path_factory):
+    """The reference's four trained checkpoints (``tests/golden/ref_ckpt``: keras_metadata.pb,
+    fingerprint.pb, variables.index and the tensor data, stored in parts of 768 KiB) put together
+    as SavedModel directories; the bundle reader's crc32c check covers the reassembled data."""
+    import shutil
+    root = tmp_path_factory.mktemp("ref_ckpt")
+    for name in REF_MODELS:
+        src, dst = os.path.join(GOLDEN, name), root / name
+        os.makedirs(dst / "variables")
+        for f in ("keras_metadata.pb", "fingerprint.pb", os.path.join("variables", "variables.index")):
+            shutil.copyfile(os.path.join(src, f), dst / f)
+        parts = sorted(f for f in os.listdir(os.path.join(src, "variables")) if f.startswith(DATA + ".part"))
+        assert parts, src
+        with open(dst / "variables" / DATA, "wb") as out:
+            for f in parts:
+                with open(os.path.join(src, "variables", f), "rb") as fh:
+                    out.write(fh.read())
+    return str(root)
 
 
 def _model(ds="cml", baseline=False):
@@ -54,9 +75,8 @@ def test_bundle_roundtrip_dtypes(tmp_path):
         read_bundle(prefix)
 
 
-@needs_ref
 @pytest.mark.parametrize("name", REF_MODELS)
-def test_reference_checkpoint_layout(name, tmp_path):
+def test_reference_checkpoint_layout(name, tmp_path, REF):
     """Every reference SavedModel loads into our module with matching shapes, and our
     writer reproduces its variables bit-exactly."""
     model, pc, mc = build_from_keras(os.path.join(REF, name))
@@ -79,8 +99,7 @@ def test_reference_checkpoint_layout(name, tmp_path):
     assert sum(1 for k in ents if k.startswith("optimizer/_variables/")) == 2 * n_train
 
 
-@needs_ref
-def test_reference_weights_forward_cpu():
+def test_reference_weights_forward_cpu(REF):
     """The trained reference CML GCN runs through our graph on CPU and gives finite,
     non-degenerate outputs (numerical parity with TF is unpinned: no TF / no data here)."""
     from gnnqc.data.synthetic import make_cml_raw
@@ -119,9 +138,8 @@ def test_save_load_resume(tmp_path):
     torch.testing.assert_close(opt3.v, opt.v)
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["model_cml", "model_cml_baseline", "model_soilnet", "model_soilnet_baseline"])
-def test_keras_metadata_matches_reference_structure(name, tmp_path):
+def test_keras_metadata_matches_reference_structure(name, tmp_path, REF):
     """keras_metadata.pb written for a model built from the reference checkpoint has the
     reference's node paths, identifiers, class names and the key layer configs."""
     from gnnqc.ckpt.keras_meta import read_keras_metadata_pb, write_keras_metadata
@@ -195,8 +213,7 @@ def test_object_graph_and_fingerprint(tmp_path):
     assert len(fp) > 40 and fp[0] == 0x08
 
 
-@needs_ref
-def test_object_graph_paths_match_reference():
+def test_object_graph_paths_match_reference(REF):
     """Every variable key of the reference's own object graph resolves along the same path in
     the graph we write for the same architecture (the variable-bearing part of the graph)."""
     import tempfile

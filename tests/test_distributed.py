@@ -86,7 +86,7 @@ def test_bench_runs_with_two_gloo_ranks():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--sensors", "8", "--days", "3", "--no-soil-line"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--sensors", "8", "--days", "3", "--no-soil-line"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
