@@ -157,4 +157,10 @@ TORCH_LIBRARY(gnnqc, m) {
   m.def("batch_gather(Tensor series, Tensor shift, Tensor scale, Tensor win_group, Tensor win_center, "
         "Tensor win_valid, Tensor wids, Tensor table, Tensor? cursor, Tensor group_adj, Tensor group_anom_pos, "
         "Tensor win_label, Tensor win_label_valid, Tensor valid_sample, int tb, int seq_len, bool time_norm) -> Tensor[]");
+  // inference: store-fed baseline front end, output stage of a scoring step (predict.hip)
+  m.def("series_tm_gather(Tensor series, Tensor shift, Tensor scale, Tensor win_group, Tensor win_center, "
+        "Tensor win_valid, Tensor win_label, Tensor group_anom_pos, Tensor wids, Tensor table, Tensor? cursor, "
+        "int tb, int seq_len, bool time_norm) -> Tensor[]");
+  m.def("predict_emit(Tensor vals, bool logits, Tensor y, Tensor mask, Tensor wid, Tensor(a!) p_out, Tensor(b!) y_out, "
+        "Tensor(c!) mask_out, Tensor(d!) wid_out, Tensor(e!) cursor) -> ()");
 }

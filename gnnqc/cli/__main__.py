@@ -4,6 +4,7 @@
     python -m gnnqc.cli preprocess --ds cml [--synthetic] [--tfrecords]
     python -m gnnqc.cli train      --ds cml [--baseline] [--synthetic] [--set model.epochs=5]
     python -m gnnqc.cli evaluate   --ds cml --model-dir models/model_cml
+    python -m gnnqc.cli predict    --ds cml --model-dir models/model_cml [--split test] [--out predictions.npz]
     python -m gnnqc.cli cv         --ds cml --folds 5 [--baseline|--both] [--synthetic]
     python -m gnnqc.cli explain    --ds cml --model-dir models/model_cml      (integrated gradients)
     python -m gnnqc.cli analyse    --xai-dir xplain/ig                         (attribution analysis)
@@ -119,6 +120,49 @@ def cmd_evaluate(args):
     print(json.dumps({"threshold": thr, "auc": auc, "mcc": mcc, "precision": prec, "recall": rec, "accuracy": acc}))
 
 
+def cmd_predict(args):
+    """Score a split with the graph-replayed inference engine and write per-window probabilities."""
+    from ..ckpt import load_model
+    from ..data.preprocessing import create_batched_dataset, load_dataset
+    from ..data.store import DeviceStore
+    from ..infer import Predictor
+    from ..parallel import dist as D
+    from ..train import flatten_predictions
+    from .common import load_configs, resolve_device
+    pc, mc = load_configs(args)
+    dev = resolve_device(args.device)
+    model = load_model(args.model_dir, device=dev)
+    baseline = type(model).__name__ == "BaselineClassifier"
+    if args.baseline and not baseline:
+        raise SystemExit(f"--baseline: {args.model_dir} holds a {type(model).__name__}")
+    ws = _windows(args, pc)
+    store = DeviceStore(ws, model.model_normalization if not baseline else model.normalization, pc.graph, device=dev)
+    if args.split == "all":
+        ids = np.arange(ws.n_windows)
+    else:
+        ids = dict(zip(("train", "val", "test"), load_dataset(pc, ws)))[args.split]
+    loader, _, _ = create_batched_dataset(ids, pc, store, shuffle=False, baseline=baseline, rank=D.rank(),
+                                          world_size=D.world_size())
+    pred = Predictor(model, store, baseline=baseline)
+    r = flatten_predictions(pred.predict(loader))
+    if D.is_main():
+        wid = r["wid"]
+        grp = ws.group_of()[wid]
+        out = {"p": r["p"], "y": r["y"], "wid": wid, "time": ws.window_dates()[wid],
+               "group": np.array([str(g.group_id) for g in ws.groups])[grp] if len(wid) else np.zeros(0, "U1")}
+        if "node" in r:
+            out["node"] = r["node"]
+            sens = [ws.groups[g].sensor_ids[n] for g, n in zip(grp, r["node"])]
+        else:
+            sens = [ws.groups[g].sensor_ids[max(ws.groups[g].anomalous_pos, 0)] for g in grp]
+        out["sensor"] = np.array([str(s) for s in sens]) if sens else np.zeros(0, "U1")
+        path = args.out or "predictions.npz"
+        np.savez(path, **out)
+        print(json.dumps({"n_windows": int(np.unique(wid).size), "n_rows": int(len(wid)), "split": args.split,
+                          "path": pred.path, "graphed": bool(pred.graphed), "out": path}))
+    D.destroy()
+
+
 def cmd_cv(args):
     from ..data.store import DeviceStore
     from ..parallel import dist as D
@@ -181,6 +225,12 @@ def main(argv=None):
     p = add_common(sub.add_parser("evaluate", help="threshold on val + test metrics of a saved model"))
     p.add_argument("--model-dir", required=True)
     p.set_defaults(fn=cmd_evaluate)
+    p = add_common(sub.add_parser("predict", help="per-window probabilities of a saved model -> .npz"))
+    p.add_argument("--model-dir", required=True)
+    p.add_argument("--baseline", action="store_true", help="the model directory holds the baseline (checked)")
+    p.add_argument("--split", choices=["train", "val", "test", "all"], default="test")
+    p.add_argument("--out", default=None, help="output file (default: predictions.npz)")
+    p.set_defaults(fn=cmd_predict)
     p = add_common(sub.add_parser("cv", help="k-fold cross validation (mean ROC-AUC)"))
     p.add_argument("--folds", type=int, default=5)
     p.add_argument("--baseline", action="store_true")

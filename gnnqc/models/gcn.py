@@ -252,22 +252,25 @@ class GCNClassifier(nn.Module):
         pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
         return store_gcn_ok(store, self.gcn_layer, self.training, pooling)
 
-    def fused_store_loss(self, store, ids, w0: float, w1: float, sums=None, hist=None):
+    def fused_store_loss(self, store, ids, w0: float, w1: float, sums=None, hist=None, return_batch: bool = False):
         """(loss, logits) of a batch given by window ids (or a device cursor into an id table)
         straight from the resident store: ONE launch for the window gather + GeneralConv +
         BatchNorm + PReLU + node pooling + concat (``gcn_fused.hip``), then the headed LSTM chain
-        of :meth:`fused_loss`. Check :meth:`store_fused_ok` first."""
+        of :meth:`fused_loss`. Check :meth:`store_fused_ok` first. ``return_batch``: also the
+        batch's ``(y, y_mask, wid)`` as the front end read them (inference writes them out)."""
         spec = self.head_spec()
         g = self.gcn_layer
         pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
         # (defer: the GCN forward runs inside the chain forward launch, as its input's producer)
-        h, M, y, ym, _ = gcn_pool_from_store(store, ids, g, self.training, pooling, defer=True)
+        h, M, y, ym, wid = gcn_pool_from_store(store, ids, g, self.training, pooling, defer=True)
         if not self.time_layer.head_chain_ok(h):
             from ..ops.head import fused_head_loss
             from ..utils.native import hip_ops
             hip_ops().gcn_prod_flush(h)
-            return fused_head_loss(self.time_layer.forward_time_major(h, M), *spec, y, ym, w0, w1, sums, hist)
-        return self.time_layer.forward_time_major_head(h, M, spec[:3], spec[3:], y, ym, w0, w1, sums, hist)
+            out = fused_head_loss(self.time_layer.forward_time_major(h, M), *spec, y, ym, w0, w1, sums, hist)
+        else:
+            out = self.time_layer.forward_time_major_head(h, M, spec[:3], spec[3:], y, ym, w0, w1, sums, hist)
+        return (*out, y, ym, wid) if return_batch else out
 
     def logits(self, inputs) -> torch.Tensor:
         z = self.head(self.features(inputs))
