@@ -27,6 +27,7 @@ import torch
 from ..data.store import CursorIds
 from ..ops import use_hip
 from ..parallel import dist as D
+from ..utils.graphs import CursorGraphs
 
 
 def series_tm_gather(store, ids):
@@ -97,12 +98,12 @@ class Predictor:
         self.use_graph = (bool(use_graph) and self.device.type == "cuda" and use_hip(store.series)
                           and store.series.dtype == torch.float32)
         self.graphed = False
-        self.graph = self.graph1 = None
-        self._key = None
-        self._table = None
+        self._steps = CursorGraphs(self._step, self.steps_per_graph, self.device, self.use_graph)
         self._out = None
-        self._cursor = torch.zeros(1, dtype=torch.long, device=self.device)
         self._path: Optional[str] = None
+
+    graph = property(lambda self: self._steps.graph)
+    graph1 = property(lambda self: self._steps.graph1)
 
     # ---------------------------------------------------------------- the scoring step
     @property
@@ -156,7 +157,7 @@ class Predictor:
             z = m(b.model_inputs(st.ds_type, self.baseline))
             y, ym, wid = b.y, b.y_mask, b.wid
             logits = False
-        predict_emit(z, logits, y, ym, wid, *self._out, self._cursor)
+        predict_emit(z, logits, y, ym, wid, *self._out, ids.cursor)
 
     # ---------------------------------------------------------------- tables and graph
     def _prepare(self, rows: torch.Tensor):
@@ -164,19 +165,20 @@ class Predictor:
         table shape changed. The table is not padded: the steps left over after the full
         ``steps_per_graph``-step replays replay a one-step graph of the same form (same table,
         same cursor), so no all-padding batch is ever scored."""
-        nb, B = int(rows.shape[0]), int(rows.shape[1])
-        key = (nb, B)
-        if self._key != key:
-            dev = self.device
+        cg = self._steps
+        if cg.load(rows)[1]:
+            nb, B = int(rows.shape[0]), int(rows.shape[1])
             R = B if self.store.per_sensor else B * self.store.n_nodes
-            self._table = torch.full((nb, B), -1, dtype=torch.long, device=dev)
+            dev = self.device
             self._out = (torch.zeros(nb, R, device=dev), torch.zeros(nb, R, device=dev),
                          torch.zeros(nb, R, device=dev), torch.full((nb, B), -1, dtype=torch.long, device=dev))
-            self._key = key
-            self.graph = self.graph1 = None
-        self._table.copy_(rows)
-        if self.use_graph and self.graph is None:
-            self._capture()
+        if cg.graph is None:                  # (always so when nothing is captured)
+            self._touch_store_tables()
+            if cg.captured:
+                # (every warm-up step starts at row 0; thread-local capture mode: a process group's
+                # watchdog thread keeps polling its events)
+                cg.capture(warm=lambda ids: (ids.cursor.zero_(), self._step(ids)), upload=True,
+                           thread_local=D.is_initialized())
 
     def _touch_store_tables(self):
         # per-window tables of the fused GCN front end: computed on first use, never inside a capture
@@ -184,30 +186,6 @@ class Predictor:
             g = self.model.gcn_layer
             pooling = "selection" if self.model.pooling_type == "selection" else self.model.aggregation_type
             self.store.gcn_fused_data(g.aggregate == "mean", {"mean": 0, "sum": 1, "selection": 2}[pooling])
-
-    def _capture(self):
-        ids = CursorIds(self._table, self._cursor)
-        self._touch_store_tables()
-        # warm up on a side stream (allocator, lazy initialisation), then capture
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._cursor.zero_()
-            for _ in range(2):
-                self._step(ids)
-        torch.cuda.current_stream().wait_stream(s)
-        # (thread-local capture mode: a process group's watchdog thread keeps polling its events)
-        kw = {"capture_error_mode": "thread_local"} if D.is_initialized() else {}
-        from ..train.engine import _graph_upload
-        graphs = []
-        for steps in (self.steps_per_graph, 1):       # the multi-step graph, and the leftover steps' one
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, **kw):
-                for _ in range(steps):
-                    self._step(ids)
-            _graph_upload(graph)
-            graphs.append(graph)
-        self.graph, self.graph1 = graphs
 
     # ---------------------------------------------------------------- the pass
     @torch.no_grad()
@@ -225,18 +203,8 @@ class Predictor:
             if nb:
                 rows = rows.to(self.device)
                 self._prepare(rows)
-                self._cursor.zero_()
-                if self.use_graph:
-                    for _ in range(nb // self.steps_per_graph):
-                        self.graph.replay()
-                    for _ in range(nb % self.steps_per_graph):
-                        self.graph1.replay()
-                    self.graphed = True
-                else:
-                    self._touch_store_tables()
-                    ids = CursorIds(self._table, self._cursor)
-                    for _ in range(nb):
-                        self._step(ids)
+                self._steps.run(0, nb)              # (from a cursor of zero: step i writes output row i)
+                self.graphed = self.use_graph
         finally:
             if was_training:
                 model.train()

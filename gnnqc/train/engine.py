@@ -22,6 +22,7 @@ from ..ops.head import fused_head_loss
 from ..ops.lstm import direct_grad_accumulation
 from ..ops.metrics import score_histogram
 from ..parallel import dist as D
+from ..utils.graphs import CursorGraphs, capture_graph, graph_upload
 from .loss import weighted_bce_with_logits
 from .resilience import FaultInjector
 
@@ -71,22 +72,6 @@ class MetricAccumulator:
         out.update(M.keras_metrics_from_counts(s[2], s[3], s[4], s[5]))
         out["auc"] = M.auc_from_hist(hist.cpu().numpy())
         return {prefix + k: v for k, v in out.items()}
-
-
-def _graph_upload(graph) -> bool:
-    """hipGraphUpload of a captured graph's executable on the current stream: the first replay of a
-    graph otherwise pays the upload of its command buffers (done here, outside any timed region).
-    False when the runtime or the executable handle is not available (no effect then)."""
-    if graph is None or not torch.cuda.is_available():
-        return False
-    try:
-        import ctypes
-        exe = graph.raw_cuda_graph_exec()
-        lib = ctypes.CDLL("libamdhip64.so")
-        rc = lib.hipGraphUpload(ctypes.c_void_p(int(exe)), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        return rc == 0
-    except Exception:         # (older torch / no HIP runtime: the first replay uploads instead)
-        return False
 
 
 class Trainer:
@@ -145,14 +130,9 @@ class Trainer:
         # device batch table with a device cursor the Adam launch advances (no host work, no id
         # copy and no graph-launch gap between those steps)
         self.graph_steps = max(1, int(os.environ.get("GNNQC_GRAPH_STEPS", "8")))
-        self.multi_graph = None
-        self._multi_key = None
-        self.multi_graph1 = None            # (one-step graph of the same form: leftover steps)
-        self._multi_key1 = None
-        self._table = None
-        self._cursor = torch.zeros(1, dtype=torch.long, device=self.device)
-        self._graph_loss = None
-        self._multi_loss = None
+        # (multi_graph, and multi_graph1: the one-step graph of the same form for the leftover steps)
+        self._steps = CursorGraphs(self._cursor_step, self.graph_steps, self.device, self.use_graph)
+        self._graph_loss = None             # (the single-step graph's loss tensor)
         # the store-fused CML step's gradient kernels all flag non-finite values: the update can
         # decide from those flags (one pass, no grid-wide barrier; gnnqc.ops.optim.FlatAdam). This is
         # the mode's eligibility; every step (and so every captured graph) re-checks that its backward
@@ -234,32 +214,30 @@ class Trainer:
             with _rf("gnnqc.optimizer"):
                 self.opt.step(grad_scale=1.0)
 
-    def _capture(self):
-        # warm up on a side stream (allocator + lazy init), then capture
+    @contextlib.contextmanager
+    def _capturing(self):
+        """Around a capture and its warm-up: the warm-up's side effects (BN running statistics, metric
+        sums, gradients) are undone, and the step count stays (capture runs nothing; replays count)."""
         snap = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        with_opt = not self.split_opt
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._body(self.static_wids, with_opt=False)
-        torch.cuda.current_stream().wait_stream(s)
-        self.graph = torch.cuda.CUDAGraph()
         it0 = self.opt.iterations
-        with torch.cuda.graph(self.graph):
-            self._body(self.static_wids, with_opt=with_opt)
-        if self.split_opt:
-            self.opt_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.opt_graph):
-                self.opt.step(grad_scale=1.0 / self.world)
-        self.opt.iterations = it0          # capture runs nothing; replays count steps
-        self._graph_loss = self.last_loss
-        # undo warm-up side effects (BN running stats, metric sums)
+        yield
+        self.opt.iterations = it0
         with torch.no_grad():
             for k, v in self.model.state_dict().items():
                 v.copy_(snap[k])
         self.train_metrics.reset()
         self.opt.zero_grad()
+
+    def _capture(self):
+        """The single-step graph over ``static_wids`` (+ the optimizer's own when it runs after the all-reduce)."""
+        def step(with_opt):
+            self._body(self.static_wids, with_opt=with_opt)
+            return self.last_loss
+
+        with self._capturing():
+            self.graph, self._graph_loss = capture_graph(lambda: step(not self.split_opt), warm=lambda: step(False))
+            if self.split_opt:
+                self.opt_graph, _ = capture_graph(lambda: self.opt.step(grad_scale=1.0 / self.world), warmups=0)
 
     def _multi_ok(self) -> bool:
         return (self.use_graph and (not self.split_opt or self.dp_graph) and self.fault is None
@@ -307,134 +285,74 @@ class Trainer:
         self.opt.zero_grad()
         return 1e3 * sum(a.elapsed_time(b) for a, b in ev) / n
 
-    def _capture_multi(self, nrows: int, steps: int = 0):
-        """Capture ``graph_steps`` full training steps (gather -> forward -> backward -> guarded
-        Adam, which advances the device cursor) as ONE graph over the static table [nrows, B].
-        ``steps=1``: the one-step graph of the same form (``multi_graph1``), which replays the
-        leftover steps of a run that is not a multiple of ``graph_steps`` from the same table and
-        cursor (the single-step graph's host id copy and launch gap cost ~10 us a step)."""
-        one = steps == 1
-        from ..data.store import CursorIds
-        snap = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        ids = CursorIds(self._table, self._cursor)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._body(ids, with_opt=False)
-                if self.dp_graph:
-                    self._reduce_grads()          # (communicator + RCCL state warm before capture)
-        torch.cuda.current_stream().wait_stream(s)
-        self.opt.zero_grad()
-        graph = torch.cuda.CUDAGraph()
-        it0 = self.opt.iterations
-        self.opt.cursor, self.opt.cursor_mod = self._cursor, nrows
-        # (thread-local capture mode: the process group's watchdog thread keeps polling its own
-        # events while this thread captures)
-        kw = {"capture_error_mode": "thread_local"} if self.dp_graph else {}
+    def _cursor_step(self, ids):
+        """One full training step by the device cursor (gather -> forward -> backward -> guarded
+        Adam, which advances the cursor): the step of the multi-step graphs."""
+        self.opt.cursor, self.opt.cursor_mod = ids.cursor, int(ids.table.shape[0])
         try:
-            with torch.cuda.graph(graph, **kw):
-                for _ in range(1 if one else self.graph_steps):
-                    if self.dp_graph:
-                        self._body(ids, with_opt=False)
-                        self._reduce_grads()
-                        self.opt.step(grad_scale=1.0 / self.world)
-                    else:
-                        self._body(ids, with_opt=True)
+            if self.dp_graph:
+                self._cursor_grads(ids)
+                self.opt.step(grad_scale=1.0 / self.world)
+            else:
+                self._body(ids, with_opt=True)
         finally:
             self.opt.cursor, self.opt.cursor_mod = None, 1
-        self.opt.iterations = it0
-        if one:
-            self.multi_graph1, self._multi_loss1 = graph, self.last_loss
-            self._multi_key1 = (nrows, self._table.shape[1])
-        else:
-            self.multi_graph, self._multi_loss = graph, self.last_loss
-            self._multi_key = (nrows, self._table.shape[1])
-        with torch.no_grad():
-            for k, v in self.model.state_dict().items():
-                v.copy_(snap[k])
-        self.train_metrics.reset()
-        self.opt.zero_grad()
+        return self.last_loss
+
+    def _cursor_grads(self, ids):
+        """That step without its update: the captures' warm-up (under DP: communicator + RCCL state)."""
+        self._body(ids, with_opt=False)
+        if self.dp_graph:
+            self._reduce_grads()
+
+    def _capture_steps(self):
+        """Capture ``graph_steps`` full training steps as ONE graph over the loaded table, and the
+        one-step graph of the same form, which replays the leftover steps of a run that is not a
+        multiple of ``graph_steps`` from the same table and cursor (the single-step graph's host id
+        copy and launch gap cost ~10 us a step)."""
+        if self.graph is None:
+            self._capture()                   # the single-step graph shares the warm allocator state
+        # (thread-local capture mode under DP: the process group's watchdog thread keeps polling its
+        # own events while this thread captures)
+        self._steps.capture(scope=self._capturing, warm=self._cursor_grads, before_capture=self.opt.zero_grad,
+                            thread_local=self.dp_graph)
+
+    multi_graph = property(lambda self: self._steps.graph)
+    multi_graph1 = property(lambda self: self._steps.graph1)
+    _cursor = property(lambda self: self._steps.cursor)
 
     def prepare_graphs(self, rows: torch.Tensor):
         """Capture the step graphs for batches drawn from ``rows`` now (outside any timed region):
-        the single-step graph and, when multi-step replay applies, the multi-step graph."""
+        the single-step graph and, when multi-step replay applies, the multi-step graphs."""
         if not self.use_graph:
             return
         if self.graph is None:
             self._capture()
         if self._multi_ok():
-            if self._table is None or tuple(self._table.shape) != tuple(rows.shape):
-                self._table, self._table_src = torch.empty_like(rows, dtype=torch.long), None
-                self.multi_graph = self.multi_graph1 = None
-            self._load_table(rows)
-            if self.multi_graph is None or self._multi_key != (int(rows.shape[0]), rows.shape[1]):
-                self._capture_multi(int(rows.shape[0]))
-            if self.multi_graph1 is None or self._multi_key1 != (int(rows.shape[0]), rows.shape[1]):
-                self._capture_multi(int(rows.shape[0]), steps=1)
+            self._steps.load(rows)
+            if self._steps.graph is None:
+                self._capture_steps()
         for g in (self.graph, self.multi_graph, self.multi_graph1):
-            _graph_upload(g)
-
-    def _load_table(self, rows: torch.Tensor):
-        """Copy the batch-id rows into the graphs' device table, unless the table already holds
-        exactly these rows (same tensor, unmodified since): a copy launch and its gap less per call."""
-        # (the source is kept referenced, so no other tensor can take its memory and pass as it)
-        src = getattr(self, "_table_src", None)
-        if src is not None and src[0] is rows and src[1] == rows._version:
-            return
-        self._table.copy_(rows, non_blocking=True)
-        self._table_src = (rows, rows._version)
+            graph_upload(g)
 
     def train_steps(self, rows: torch.Tensor, start: int, k: int):
         """``k`` training steps on batches ``rows[(start + i) % len(rows)]`` (rows: [n, B] device
-        ids). With graphs, full chunks of ``graph_steps`` steps replay one multi-step graph each;
-        the rest (and every step when fault injection or DP is on) go through :meth:`train_step`."""
-        nb = int(rows.shape[0])
-        S = self.graph_steps
-        one_ok = (self.multi_graph1 is not None and self._multi_ok() and self._table is not None
-                  and tuple(self._table.shape) == tuple(rows.shape) and self._multi_key1 == (nb, rows.shape[1]))
-        if k < S and one_ok:                 # (prepare_graphs captured the one-step form)
-            self.model.train()
-            self._load_table(rows)
-            self._cursor.fill_(start % nb)
-            for _ in range(k):
-                self.multi_graph1.replay()
-            self.opt.iterations += k
-            self.global_step += k
-            self.last_loss = self._multi_loss1
-            return self.last_loss
-        if not self._multi_ok() or k < S:
+        ids). With graphs, full chunks of ``graph_steps`` steps replay one multi-step graph each and
+        the rest the one-step graph of the same form; every step goes through :meth:`train_step`
+        when fault injection or gloo DP is on, and when fewer than ``graph_steps`` steps are asked
+        for with no graphs captured for these rows."""
+        if not self._multi_ok() or (k < self.graph_steps and not self._steps.holds(rows)):
+            nb = int(rows.shape[0])
             for i in range(k):
                 self.train_step(rows[(start + i) % nb])
             return self.last_loss
         self.model.train()
-        if self._table is None or tuple(self._table.shape) != tuple(rows.shape):
-            self._table, self._table_src = torch.empty_like(rows, dtype=torch.long), None
-            self.multi_graph = self.multi_graph1 = None
-            one_ok = False
-        if self.multi_graph is not None and self._multi_key != (nb, rows.shape[1]):
-            self.multi_graph = None
-        self._load_table(rows)
-        if self.multi_graph is None:
-            if self.graph is None:
-                self._capture()              # the single-step graph shares the warm allocator state
-            self._capture_multi(nb)
-        self._cursor.fill_(start % nb)
-        n = k // S
-        for _ in range(n):
-            self.multi_graph.replay()
-        self.opt.iterations += n * S
-        self.global_step += n * S
-        self.last_loss = self._multi_loss
-        if k > n * S and one_ok:             # leftover steps: the one-step graph, same table and cursor
-            for _ in range(k - n * S):
-                self.multi_graph1.replay()
-            self.opt.iterations += k - n * S
-            self.global_step += k - n * S
-            self.last_loss = self._multi_loss1
-            return self.last_loss
-        for i in range(n * S, k):
-            self.train_step(rows[(start + i) % nb])
+        self._steps.load(rows)
+        if self._steps.graph is None:
+            self._capture_steps()
+        self.last_loss = self._steps.run(start, k)[2]
+        self.opt.iterations += k
+        self.global_step += k
         return self.last_loss
 
     def train_step(self, wids: torch.Tensor):

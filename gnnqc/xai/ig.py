@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from .. import config as C
+from ..utils.graphs import capture_graph
 
 CONFUSION = {(0, 0): "TN", (0, 1): "FP", (1, 0): "FN", (1, 1): "TP"}
 
@@ -152,17 +153,11 @@ class IntegratedGradients:
             self._graph = None
             static = dataclasses.replace(batch, **{f: (None if t is None else t.clone())
                                                    for f, t in zip(self._GRAPH_FIELDS, ts)})
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):                    # allocator + lazy init outside the capture
-                    self._attribute(static, None)
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                out = self._attribute(static, None)
-            self._graph = (key, g, static, out)
-        _, g, static, out = self._graph
+            g, out = capture_graph(lambda: self._attribute(static, None))
+            # (the record owns the backward seed the capture read by address: an _attribute call of
+            # another shape replaces self._ones, and must not free this one)
+            self._graph = (key, g, static, out, getattr(self, "_ones", None))
+        _, g, static, out = self._graph[:4]
         for f, t in zip(self._GRAPH_FIELDS, ts):
             if t is not None:
                 getattr(static, f).copy_(t, non_blocking=True)
