@@ -1501,16 +1501,19 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
   };
   const size_t eoff = (size_t)row0 * H + tid;        // this lane's dh element in a [Mp][H] row block
   const size_t hstep = (size_t)Mp * H;
-  auto load = [&](int J, int SS) {
+  auto load_dh = [&](int J, int SS) {
     const int tt = max(T - 1 - SS, 0);
-    const size_t o = sidx(tt);
-    rg[J] = *reinterpret_cast<const uint2*>(S.g + o * 4);
-    rc[J] = S.c[o];
     const int st = max(src_t(tt), 0);
     if constexpr (SRC) rq[J] = ld_granule(S.din + eoff + (size_t)st * hstep);
     else rq[J] = (unsigned long long)__float_as_uint(S.dh[eoff + (size_t)st * hstep]);
     if constexpr (UP) ri[J] = (unsigned)S.pidx[eoff + (size_t)st * hstep];
     else ri[J] = 0u;
+  };
+  auto load = [&](int J, int SS) {
+    const size_t o = sidx(max(T - 1 - SS, 0));
+    rg[J] = *reinterpret_cast<const uint2*>(S.g + o * 4);
+    rc[J] = S.c[o];
+    load_dh(J, SS);
   };
   // dh of time tt from ring slot J (tag-checked for a stream source)
   auto stage_dh = [&](int J, int tt) -> float {
@@ -1565,11 +1568,196 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
     const int st = src_t(tw);
     if (st >= 0) (void)chain_wait(S.din + eoff + (size_t)st * hstep, tagb | (unsigned)st, ctl);
   }
+  if constexpr (!SK) {
+    // ------------------------------------------------------------------ H = 16: the pipelined step
+    // The bottom layers' T reverse steps are the backward's critical path, so between two barriers only
+    // what needs dh_rec stays behind the MFMAs, and the hand-off staging runs while LDS reads fly:
+    //
+    //   barrier s                      dz(s) is in zs[s & 1], dh(s + 1) in dhs[(s + 1) & 1]
+    //   ds_read_b128 of dz(s) K-block 0, MFMA as soon as it is there
+    //   ds_read_b128 of K-block 1 and the read of dh(s + 1)
+    //     while they fly: dh(s + 2) from its ring slot (tag check, un-pool select) -> dhs[s & 1],
+    //                     ring load of dh(s + 2 + D)
+    //   second MFMA: dh_rec = U dz(s)
+    //     in its shadow: gates of step s + 1 unpacked, tanh(c), every factor that does not need dh_rec
+    //   dh = dh(s + 1) + dh_rec, dct, dc, four products, bf16, dz(s + 1) -> zs[(s + 1) & 1]
+    //   state load of step s + 1 + D into the slot just consumed
+    //
+    // dhs[s & 1] was last read after barrier s - 1 and is read again after barrier s + 1, so two
+    // buffers suffice. Steps past the sequence (s >= T, and the un-pooling tail past the last pooling
+    // window) carry no source granule: they are never waited for and stage a zero. The hoisted
+    // factors reassociate the cell's products (dct * (g * i * (1 - i)) for ((dct * g) * i) * (1 - i)):
+    // bf16 rounding flips in dz against the per-layer kernels, nothing else.
+    // Measured placements (profiles/chain_bwd_h16_pipeline_ab.txt): both K-block reads ahead of the
+    // first MFMA, tanh(c) ahead of the MFMAs, the state load pinned behind the dz stores or moved into
+    // the MFMA shadow, chain_wait inlined, a ring of 2 / 3 / 5 / 6 steps: all slower than this order.
+    // Wave-uniform cursors replace the per-step address products: the saved state and the dh source
+    // are walked one step at a time, and every load is a fixed base, a 32-bit step offset and a lane
+    // offset (the arrays of an H = 16 stage stay below 4 GiB: lstm_chain_bwd checks it).
+    static_assert(PUBW && D >= 2, "H = 16 stage: publisher waves, ring of at least two steps");
+    constexpr unsigned NOSRC = 0xFFFFFFFFu;
+    const unsigned lo8 = (unsigned)((tile * NW + w) * 64 + lane) * 8u;    // this lane's cell in a state step (bytes of g)
+    const unsigned gstr = (unsigned)(ntiles * NW * 64 * 8);               // bytes per step of g (c: half)
+    const char* gbase = reinterpret_cast<const char*>(S.g);
+    const char* cbase = reinterpret_cast<const char*>(S.c);
+    int stt = T - 1;                                                      // time of the next state load
+    auto state_load = [&](int J) {
+      const unsigned o = (unsigned)__builtin_amdgcn_readfirstlane(stt) * gstr + lo8;   // (a scalar product)
+      rg[J] = *reinterpret_cast<const uint2*>(gbase + o);
+      rc[J] = *reinterpret_cast<const float*>(cbase + (o >> 1));
+      stt = max(stt - 1, 0);                                              // (steps past the sequence reload t = 0)
+    };
+    // dh source cursor: time dtt (< 0 past the sequence), source row dst and phase dph = dtt - dst P of
+    // an un-pooling stage (dph >= P: the tail past the last pooling window, read from the last row)
+    constexpr unsigned ESZ = SRC ? 8 : 4;
+    const unsigned eo = (unsigned)eoff;
+    const unsigned hrow = (unsigned)hstep;
+    const char* dbase = SRC ? reinterpret_cast<const char*>(S.din) : reinterpret_cast<const char*>(S.dh);
+    const char* pbase = reinterpret_cast<const char*>(S.pidx);
+    int dtt = T - 1;
+    int dst = UP ? min(divp(dtt), Ts - 1) : dtt;
+    int dph = UP ? dtt - dst * P : 0;
+    const unsigned dlim = (unsigned)(UP ? Ts * P : T);                    // times with a source granule: [0, dlim)
+    unsigned rinf[D];                 // per ring slot: phase << 12 | source row, NOSRC: no source granule
+    auto ring_load = [&](int J) {
+      const unsigned o = (unsigned)max(dst, 0) * hrow + eo;
+      if constexpr (SRC) rq[J] = ld_granule(reinterpret_cast<const unsigned long long*>(dbase + o * ESZ));
+      else rq[J] = (unsigned long long)__float_as_uint(*reinterpret_cast<const float*>(dbase + o * ESZ));
+      if constexpr (UP) ri[J] = (unsigned)*reinterpret_cast<const unsigned char*>(pbase + o);
+      else ri[J] = 0u;
+      const unsigned inf = ((unsigned)dph << 12) | (unsigned)dst;
+      rinf[J] = (unsigned)dtt < dlim ? inf : NOSRC;
+      --dtt;
+      if constexpr (UP) {
+        const bool wrap = dph == 0;                                       // the source row changes
+        dst = wrap ? dst - 1 : dst;
+        dph = wrap ? P - 1 : dph - 1;
+      } else {
+        --dst;
+      }
+    };
+    auto stage = [&](int J) -> float {
+      const unsigned inf = rinf[J];
+      const bool has = inf != NOSRC;
+      if constexpr (SRC) {
+        const unsigned want = tagb | (inf & 0xfffu);
+        const bool bad = has && (unsigned)(rq[J] >> 32) != want;
+        if (__builtin_amdgcn_ballot_w64(bad) != 0) {
+          rq[J] = chain_wait(S.din + eoff + (size_t)(inf & 0xfffu) * hstep, want, ctl);
+        }
+      }
+      const float v = __uint_as_float((unsigned)rq[J]);
+      bool keep = has;
+      if constexpr (UP) keep = keep && ri[J] == (inf >> 12);
+      return keep ? v : 0.f;
+    };
+    // the cell of one step in two halves: what the saved state alone gives, and what needs dh_rec
+    // (tanh(c) stays a statement of its own: folded into cell_pre as a local the compiler scheduled the
+    // step differently, same-box 0.2383-0.2403 against 0.2350-0.2360 ms/step)
+    float tc, fo, ff, z0, z1, z2, z3;
+    auto cell_pre_c = [&](int J) { tc = tanhf_fast(rc[J]); };
+    auto cell_pre = [&](int J, int JN, int tt) {
+      const float cp = rc[JN] * (tt > 0 ? 1.f : 0.f);                     // c_{t-1}
+      const float4 g4 = gates_unpack(rg[J]);
+      fo = g4.w * (1.f - tc * tc);
+      ff = g4.y;
+      z0 = g4.z * g4.x * (1.f - g4.x);
+      z1 = cp * g4.y * (1.f - g4.y);
+      z2 = g4.x * (1.f - g4.z * g4.z);
+      z3 = tc * g4.w * (1.f - g4.w);
+    };
+    float dc = 0.f;
+    auto cell_tail = [&](int pb, float dh) {
+      const float dct = dc + dh * fo;
+      dc = dct * ff;
+      zs[pb][col][chz(col, 0 * H + unit)] = (__bf16)(dct * z0);
+      zs[pb][col][chz(col, 1 * H + unit)] = (__bf16)(dct * z1);
+      zs[pb][col][chz(col, 2 * H + unit)] = (__bf16)(dct * z2);
+      zs[pb][col][chz(col, 3 * H + unit)] = (__bf16)(dh * z3);
+    };
+
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      state_load(j);
+      ring_load(j);
+    }
+    __syncthreads();
+    dhs[0][tid / H][tid % H] = stage(0);          // dh of steps 0 and 1
+    ring_load(0);
+    dhs[1][tid / H][tid % H] = stage(1);
+    ring_load(1);
+    __syncthreads();
+    float dhn = dhs[0][col][unit];
+    if (tid == 0 && S.trace_mid) S.trace_mid[blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
+    cell_pre_c(0);
+    cell_pre(0, 1, T - 1);                        // step 0: no dh_rec yet
+    cell_tail(0, dhn);
+    state_load(0);
+
+    long long* pr = (S.prof != nullptr && tile == 0) ? S.prof : nullptr;
+    for (int s0 = 0; s0 < T; s0 += D) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const int s = s0 + j;
+        const int p = s & 1;
+        const int j1 = (j + 1) % D, j2 = (j + 2) % D;
+        lds_barrier();
+        chain_mark(pr, s, 0);
+        const bf16x8_t bz0 = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 8 * quad)]);
+        __builtin_amdgcn_sched_barrier(0);         // (the fences keep this order: see the stage's header)
+        f32x4_t a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[0], bz0, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        const bf16x8_t bz1 = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 + 8 * quad)]);
+        dhn = dhs[p ^ 1][col][unit];
+        dhs[p][tid / H][tid % H] = stage(j2);     // dh of step s + 2, then its slot's next load
+        ring_load(j2);
+        chain_mark(pr, s, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        const f32x4_t a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[1], bz1, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        cell_pre_c(j1);
+        cell_pre(j1, j2, T - 2 - s);
+        __builtin_amdgcn_sched_barrier(0);
+        float dhr = a0[0] + a1[0];
+#ifdef GQ_CHAIN_PROF
+        if (pr != nullptr) asm volatile("" : "+v"(dhr));
+#endif
+        chain_mark(pr, s, 2);
+        cell_tail(p ^ 1, dhn + dhr);
+        chain_mark(pr, s, 3);
+        state_load(j1);
+        if constexpr (!DXW) {                      // dx^T = W dz^T of step s (DXW: the dx wave's)
+          if (s < T) {
+#pragma unroll
+            for (int q = 0; q < TX; ++q) {
+              const int xb = w + NW * q;
+              if (xb < NXB) {
+                f32x4_t a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                  const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 * k + 8 * quad)]);
+                  bf16x8_t wa;
+                  if constexpr (L::WL) wa = *reinterpret_cast<const bf16x8_t*>(&wl[xb][col][32 * k + 8 * quad]);
+                  else wa = wfr[q][k];
+                  a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, bz, a, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dxs[p][col][16 * xb + 4 * quad + r] = a[r];
+              }
+            }
+          }
+        }
+        chain_mark(pr, s, 4);
+      }
+    }
+    __syncthreads();
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < D; ++j) load(j, j);
   __syncthreads();
   dhs[0][tid / H][tid % H] = stage_dh(0, T - 1);
-  load(0, D);
+  load_dh(0, D);                     // (the dh slot alone: the state of step 0 is still to be used)
   float dc = 0.f, dhr = 0.f, dhn;
   __syncthreads();
   dhn = dhs[0][col][unit];
@@ -1634,18 +1822,6 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
           dpart[kg][col][16 * ut + 4 * quad + r] = a[r];
           xpart[p][kx][col][16 * xt + 4 * quad + r] = b[r];
         }
-      } else {   // serial chain: dh_{t-1} = U dz_t
-        f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 * k + 8 * quad)]);
-          if (k & 1) a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[k], bz, a1, 0, 0, 0);
-          else a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[k], bz, a0, 0, 0, 0);
-        }
-        dhr = a0[0] + a1[0];
-#ifdef GQ_CHAIN_PROF
-        if (pr != nullptr) asm volatile("" ::"v"(dhr));
-#endif
       }
       chain_mark(pr, s, 4);
       if constexpr (!PUBW) {   // dz tile -> HBM (weight-gradient pass; else the publisher stores it)
@@ -1663,24 +1839,6 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
 #pragma unroll
         for (int g = 0; g < KG; ++g) sdh += dpart[g][col][unit];
         dhr = sdh;
-      } else if (!DXW && t >= 0) {   // dx^T = W dz^T of this step (DXW: the dx wave's)
-#pragma unroll
-        for (int q = 0; q < TX; ++q) {
-          const int xb = w + NW * q;
-          if (xb < NXB) {
-            f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < KB; ++k) {
-              const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 * k + 8 * quad)]);
-              bf16x8_t wa;
-              if constexpr (L::WL) wa = *reinterpret_cast<const bf16x8_t*>(&wl[xb][col][32 * k + 8 * quad]);
-              else wa = wfr[q][k];
-              a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, bz, a, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dxs[p][col][16 * xb + 4 * quad + r] = a[r];
-          }
-        }
       }
       chain_mark(pr, s, 5);
     }
@@ -2671,6 +2829,8 @@ static std::vector<at::Tensor> chain_bwd_setup(ChainBArgs& A, std::vector<at::Te
     check_gates_cuda(g[s]);
     TORCH_CHECK(g[s].numel() == (long)(T + 1) * Mp * H * 4 && c[s].numel() == (long)(T + 1) * Mp * H,
                 "lstm_chain_bwd: saved state shapes");
+    // (the H = 16 stages address their saved state and their dh source with 32-bit byte offsets)
+    TORCH_CHECK(H != 16 || (long)(T + 1) * Mp * H * 8 < (1L << 32), "lstm_chain_bwd: stage ", s, " state too large");
     const int Ts = P > 0 ? T / P : T;
     if (s == 0) {
       TORCH_CHECK(dh.size(0) == Ts && dh.size(2) == H, "lstm_chain_bwd: dh shape");

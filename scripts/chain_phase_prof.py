@@ -2,8 +2,11 @@
 """Per-step phase clocks of the chain kernels' stages (GNNQC_CHAIN_PROF=1; tile 0, wave 0,
 s_memtime ticks): median over the first 64 steps of every phase of the step loop, per stage.
 Forward marks (compute wave 0): 0 loop top, 1 pre-activations out of the MFMAs, 2 gates / cell /
-outputs stored, 3 after the step barrier. Backward: 0 top, 1 cell phase done, 2 next dh staged,
-3 after the barrier, 4 dh_rec (U dz) ready, 5 dx MFMAs done. One JSON line per launch kind."""
+outputs stored, 3 after the step barrier. Backward, split-K stages (H >= 32): 0 top, 1 cell phase
+done, 2 next dh staged, 3 after the barrier, 4 partial products stored, 5 dh_rec ready. Backward,
+H = 16 stages (their step starts at the barrier): 0 after the barrier, 1 dh of step s + 2 staged and
+its ring load issued, 2 dh_rec (U dz) ready, 3 dz of step s + 1 written, 4 state load issued (the
+rest of the step is the wait at the next barrier). One JSON line per launch kind."""
 import json
 import os
 import sys
@@ -96,8 +99,7 @@ def main():
         ops.lstm_chain_head_bwd(one, xt, h4, g4, c4, Ws[6], Us[6], pk, hb, head, y, mask, M, *hc, hg, *chain_args)
     torch.cuda.synchronize()
     pb = ops.lstm_chain_prof(x).cpu()
-    # H = 16 stages (chain_bwd_stage_io) mark 0 top, 1 cell done, 2 after the barrier, 3 dh_rec ready,
-    # 4 dx done; the split-K stages (H >= 32) 0..5 as in the docstring
+    # (five marks per stage: the H = 16 stages write 0..4, the split-K stages 0..5, see the docstring)
     print(json.dumps({"launch": "bwd (time4 stage + chain6)", "stages": phases(pb, 5)}), flush=True)
     # H = 16 stages' I/O waves: marks 5..7 = staging start, tile staged, next loads issued
     # (non-I/O H = 16 stages: m6 the dx wave's tile is in LDS, m7 the publisher's stores are issued)
