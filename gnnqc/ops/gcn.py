@@ -152,7 +152,8 @@ class _HipGCNPool(torch.autograd.Function):
 def gcn_pool_hip_ok(x, W, aggregate: str, pooling: str, dropout: float, training: bool) -> bool:
     from . import use_hip
     linear = aggregate in ("mean", "sum") and pooling in ("mean", "sum", "selection")
-    return bool(use_hip(x) and linear and not (dropout and training) and x.shape[-1] <= 8
+    # (1..4 input channels: what gcn_prep instantiates, gcn_glue.hip GQ_GLUE_CIN_DISPATCH)
+    return bool(use_hip(x) and linear and not (dropout and training) and x.shape[-1] <= 4
                 and W.shape[1] in (8, 16, 32))
 
 

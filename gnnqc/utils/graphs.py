@@ -9,6 +9,7 @@
 from __future__ import annotations
 
 import contextlib
+import gc
 
 import torch
 
@@ -47,8 +48,21 @@ def capture_graph(body, warm=None, warmups: int = 2, before_capture=None, thread
     if before_capture is not None:
         before_capture()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, **({"capture_error_mode": "thread_local"} if thread_local else {})):
-        out = body()
+    # No cyclic garbage collection may run between capture_begin and capture_end: a dead cycle that
+    # holds an earlier CUDAGraph (a dropped Trainer / Predictor) is destroyed by whichever thread the
+    # collector happens to run on - the autograd worker too - and releasing a graph's memory pool is
+    # a runtime call a capturing stream does not allow; the error is raised in a destructor and ends
+    # the process. torch.cuda.graph() collected before capture_begin up to torch 2.8 and no longer
+    # does, so: collect now, and keep the collector off until the capture has ended.
+    gc.collect()
+    gc_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **({"capture_error_mode": "thread_local"} if thread_local else {})):
+            out = body()
+    finally:
+        if gc_on:
+            gc.enable()
     return graph, out
 
 

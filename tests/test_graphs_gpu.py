@@ -127,3 +127,42 @@ def test_ig_graph_owns_its_backward_seed(cuda_device, cml_windows):
     for k in ("grad_x", "grad_anom", "pred", "path_pred"):
         err = (third[k] - first[k]).abs().max().item()
         assert err <= 1e-5 * first[k].abs().max().item() + 1e-7, (k, err)
+
+
+def test_capture_graph_keeps_the_garbage_collector_off_while_capturing(cuda_device):
+    """capture_graph collects dead cycles before capture_begin and keeps the cyclic collector off
+    until capture_end (an automatic collection on any thread in between could destroy an earlier
+    graph, which a capturing stream does not allow), then restores the collector's state."""
+    import gc
+
+    from gnnqc.utils.graphs import capture_graph
+    buf = torch.zeros(8, device=cuda_device)
+    seen = []
+
+    class Node:
+        pass
+
+    a, b = Node(), Node()
+    a.other, b.other = b, a                              # a dead cycle once the names are dropped
+    import weakref
+    alive = weakref.ref(a)
+    del a, b
+
+    def body():
+        seen.append((gc.isenabled(), alive() is None, torch.cuda.is_current_stream_capturing()))
+        buf.add_(1)
+        return buf
+
+    assert gc.isenabled()
+    graph, out = capture_graph(body, warm=lambda: None, warmups=1)
+    assert seen == [(False, True, True)]                 # collector off, cycle already collected
+    assert gc.isenabled() and out is buf
+    graph.replay()
+    torch.cuda.synchronize()
+    assert buf.tolist() == [1.0] * 8                     # (captured work runs at replay only)
+    gc.disable()
+    try:                                                 # a caller that had it off keeps it off
+        capture_graph(body, warm=lambda: None, warmups=1)
+        assert not gc.isenabled()
+    finally:
+        gc.enable()
