@@ -69,9 +69,6 @@ static constexpr int CHAIN_SPIN = 1 << 20;
 #ifndef CHAIN_LD16
 #define CHAIN_LD16 0         // 1: one 16-byte buffer load per granule pair (measured: stale reads, ~4.5k re-polls per launch)
 #endif
-#ifndef CHAIN_DEFER_LD
-#define CHAIN_DEFER_LD 1     // I/O waves issue their next loads a step after staging (see the I/O loops)
-#endif
 #ifndef CHAIN_W_SLEEP
 #define CHAIN_W_SLEEP 0      // chain_wait back-off: s_sleep argument (x 64 clocks) per nap unit (8 / 8: 0.284 ms/step,
 #endif
@@ -80,9 +77,6 @@ static constexpr int CHAIN_SPIN = 1 << 20;
 #endif
 #ifndef CHAIN_RP_NAPMAX
 #define CHAIN_RP_NAPMAX 16   // bulk re-poll of a stale tile: largest nap (s_sleep 2 units) between rounds
-#endif
-#ifndef CHAIN_H64_CPL2
-#define CHAIN_H64_CPL2 1     // H = 64 forward stages: two cells per lane on 8 compute waves (see ChainCfg)
 #endif
 #ifndef CHAIN_PRIO
 #define CHAIN_PRIO 2         // s_setprio of the compute waves of a stage with I/O waves
@@ -162,12 +156,7 @@ __device__ __forceinline__ void st_granule(unsigned long long* p, float v, unsig
 // memory system enough to slow the running stages' own streams severalfold.)
 template <bool INL>
 __device__ __forceinline__ unsigned long long chain_wait_body(const unsigned long long* p, unsigned want, int* ctl);
-#ifdef CHAIN_WAIT_INLINE
-__device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
-unsigned long long chain_wait(const unsigned long long* p, unsigned want, int* ctl) {
+__device__ __noinline__ unsigned long long chain_wait(const unsigned long long* p, unsigned want, int* ctl) {
   return chain_wait_body<false>(p, want, ctl);
 }
 // inlined form for the forward I/O waves: a call in their step loop made the compiler drain vmcnt
@@ -249,11 +238,9 @@ struct ChainLds {
   static constexpr int HS = 2 * 16 * (TMC<H>::KPH + 8) * 2;
   static constexpr int XS = 2 * 16 * (32 * KX + 8) * 2;
   static constexpr int HF = 2 * 16 * TMC<H>::HP * 4;
-  // (stages with a publisher wave: H <= 32, and H = 64 in its two-cells-per-lane layout) the cells'
-  // packed gates and c of two steps
-  static constexpr bool PUB = H <= 32 || CHAIN_H64_CPL2;
-  static constexpr int GS = PUB ? 2 * 16 * H * 8 : 0;
-  static constexpr int CS = PUB ? 2 * 16 * H * 4 : 0;
+  // the cells' packed gates and c of two steps (staged for the publisher wave)
+  static constexpr int GS = 2 * 16 * H * 8;
+  static constexpr int CS = 2 * 16 * H * 4;
   static constexpr int BYTES = HS + XS + HF + GS + CS;
 };
 constexpr int chain_max2(int a, int b) { return a > b ? a : b; }
@@ -276,10 +263,11 @@ __device__ __forceinline__ float chain_gate_scale(int ag) { return ag == 2 ? -2.
 // LDS tile of the next step. (A register ring of D slots in one wave was the first form: the
 // compiler's wait insertion drained the whole ring at the top of every unrolled round.) For a last
 // stage that pools its own output, I/O wave 0 pools h from the fp32 LDS tile. One LDS barrier per
-// step. H = 64 fills a 1024-thread workgroup with compute waves: there every thread also streams x
-// through a D-slot register ring, as one role.
-// (only when they fit the 1024-thread workgroup and a lane's share of one step's tile - ngl granules
-// of pin steps each - stays within 24 registers pairs; else every thread streams, as for H = 64)
+// step. Without I/O waves every thread also streams x through a D-slot register ring, as one role.
+// (I/O waves only when they fit the 1024-thread workgroup and a lane's share of one step's tile - ngl
+// granules of pin steps each - stays within 24 registers pairs. Every stage of the dispatch table has
+// them at the default ring depths; a deeper ring reaches the one-role form, e.g. CHAIN_D = 8 at
+// H = 32 / 64: 512 + 64 * 8 + 64 threads.)
 __host__ __device__ constexpr int chain_io_waves(int nt, int d, int ngl = 1, int pin = 1) {
   return nt + 64 * d + 64 <= 1024 && ngl * pin <= 12 ? d : 0;   // (+ the publisher wave)
 }
@@ -287,10 +275,10 @@ __host__ __device__ constexpr int chain_io_waves(int nt, int d, int ngl = 1, int
 // (and so does a 64-channel input of an H = 64 stage, 8 granule pairs per lane in one wave: its I/O
 // waves' registers spilled; with two waves per step the ring is 3 steps deep to fit the workgroup)
 __host__ __device__ constexpr int chain_io_group(int pin, int kx = 1, int h = 16) {
-  return pin > 1 || (h == 64 && kx == 2 && CHAIN_H64_CPL2) ? 2 : 1;
+  return pin > 1 || (h == 64 && kx == 2) ? 2 : 1;
 }
 __host__ __device__ constexpr int chain_stage_d(int h, int kx, int d) {
-  return h == 64 && kx == 2 && CHAIN_H64_CPL2 && d > 3 ? 3 : d;
+  return h == 64 && kx == 2 && d > 3 ? 3 : d;
 }
 // threads of a stage workgroup that run the stage (compute + I/O waves + the publisher)
 __host__ __device__ constexpr int chain_live_threads(int nt, int d, int kx, bool src, int pin, int h = 16) {
@@ -311,7 +299,7 @@ __host__ __device__ constexpr int chain_live_threads(int nt, int d, int kx, bool
 // one-cell-per-lane layout of the backward (cell (wave gi, lane), gi = compute wave + NW * cc).
 template <int H>
 struct ChainCfg {
-  static constexpr int CPL = (H == 64 && CHAIN_H64_CPL2) ? 2 : 1;
+  static constexpr int CPL = H == 64 ? 2 : 1;
   static constexpr int NW = H / 4 / CPL, NT = 64 * NW, G4 = 4 * H;
   static constexpr int KSH = TMC<H>::KSH, KPH = TMC<H>::KPH, HP = TMC<H>::HP;
   static constexpr int NWV = H / 4, NCELL = 64 * NWV;     // the saved-state layout's waves / cells per tile
@@ -566,7 +554,7 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
   __syncthreads();
   if (IOW ? (streamer && iow == 0) : streamer) {
     stage_x(0, 0, 0);
-    if (!IOW || !CHAIN_DEFER_LD) load_x(0, min(D, T - 1));
+    if (!IOW) load_x(0, min(D, T - 1));
   }
   float c[CPL];
 #pragma unroll
@@ -596,7 +584,7 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
       acc[cc] = accx + acch;
     }
     chain_mark(pr, t, 1);
-    if constexpr (DOI) {                 // (H = 64: every thread also streams x through its ring)
+    if constexpr (DOI) {                 // (no I/O waves: every thread also streams x through its ring)
       stage_x(p ^ 1, rn, min(t + 1, T - 1));
       load_x(rn, min(t + 1 + D, T - 1));
     }
@@ -681,7 +669,7 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
       int kt = (iow + D - 1) % D;        // steps until this wave's turn: t = kt, kt + D, ...
       int next_ld = iow == 0 ? D : -1;   // (group 0 staged x_0 in the prologue)
       for (int t = 0; t < T; ++t) {
-        if (CHAIN_DEFER_LD && next_ld >= 0) {
+        if (next_ld >= 0) {
           load_x(0, min(next_ld, T - 1));
           next_ld = -1;
         }
@@ -689,8 +677,7 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
           if (iot == 0) chain_mark_wave(pr, t, 4);
           stage_x((t + 1) & 1, 0, t + 1);
           if (iot == 0) chain_mark_wave(pr, t, 5);
-          if (CHAIN_DEFER_LD) next_ld = t + 1 + D;
-          else load_x(0, min(t + 1 + D, T - 1));
+          next_ld = t + 1 + D;
           if (iot == 0) chain_mark_wave(pr, t, 6);
         }
         kt = kt == 0 ? D - 1 : kt - 1;
@@ -994,18 +981,11 @@ __global__ __launch_bounds__(1024) void lstm_chain_fwd_kernel(ChainArgs A) {
     if (threadIdx.x >= chain_live_threads(ChainCfg<HH>::NT, DS, KXX, SRCV, PINV, HH)) return; \
     chain_stage<HH, TRAIN, KXX, DS, SRCV, PINV>(S, tile, A.ntiles, A.Mp, tagb, A.ctl, smem); \
   }
-#ifdef CHAIN_KX1_ONLY      // (A/B probe: no 33-64-channel stage bodies in the kernel; such chains fail)
-#define GQ_CHAIN_SRC(HH, PINV, DD) if (KX == 1) GQ_CHAIN_BODY(HH, 1, DD, true, PINV)
-#define GQ_CHAIN_KX(HH)                                                                 \
-  if (src) { if (S.PIN == 3) { GQ_CHAIN_SRC(HH, 3, CHAIN_D3) } else { GQ_CHAIN_SRC(HH, 1, CHAIN_D) } } \
-  else { if (KX == 1) GQ_CHAIN_BODY(HH, 1, CHAIN_D0, false, 1) }
-#else
 #define GQ_CHAIN_SRC(HH, PINV, DD)                                                      \
   if (KX == 1) GQ_CHAIN_BODY(HH, 1, DD, true, PINV) else GQ_CHAIN_BODY(HH, 2, DD, true, PINV)
 #define GQ_CHAIN_KX(HH)                                                                 \
   if (src) { if (S.PIN == 3) { GQ_CHAIN_SRC(HH, 3, CHAIN_D3) } else { GQ_CHAIN_SRC(HH, 1, CHAIN_D) } } \
   else { if (KX == 1) GQ_CHAIN_BODY(HH, 1, CHAIN_D0, false, 1) else GQ_CHAIN_BODY(HH, 2, CHAIN_D0, false, 1) }
-#endif
   if (H == 16) GQ_CHAIN_KX(16)
   else if (H == 32) GQ_CHAIN_KX(32)
   else GQ_CHAIN_KX(64)
@@ -1036,11 +1016,9 @@ struct ChainBStage {
   float* dx;                         // last stage: fp32 dx [T][Mp][Din]
   long long* trace_mid;              // profiling: time the step loop starts
   long long* prof;                   // profiling (GNNQC_CHAIN_PROF=1): tile 0's per-step phase clocks
-  // producer-side un-pooling (uidx != nullptr): the MaxPooling1D(uP) between this stage's input and the
-  // stage below is undone HERE - its argmax bytes [T][Mp][Din] are staged in LDS once and every dx
-  // element is published as uP full-resolution granules (value at the argmax step, 0 elsewhere) into a
-  // [uT][Mp][Din] stream, so the stage below (punp = 1) streams plain dh with no argmax load or select
-  // on its recurrence
+  // Unused, always zero: the arguments of the retired producer-side un-pooling (profiles/README.md).
+  // They and the kernel's punp test stay for now: without them the kernel-argument layout shifts, and
+  // that build measured 0.2374 against 0.2343 ms/step on one box (profiles/chain_variant_retirement.txt)
   const unsigned char* uidx;
   int uP, uT, punp;
   int H, T, Din, Dw, KX, P, Ts;
@@ -1080,19 +1058,15 @@ static_assert(sizeof(ChainBArgs) <= 4096, "chain backward kernel arguments");
 #ifndef CHAINB_XPAD
 #define CHAINB_XPAD 1
 #endif
-#ifndef CHAINB_ZSWZ
-#define CHAINB_ZSWZ 0    // swizzled dz tile: same-box CML 0.2477 vs 0.2459 ms unswizzled (profiles/r6_zs_swizzle_ab.txt)
-#endif
-template <int H, int KX>
-struct ChainBLds {
-  static constexpr bool WL = H >= 32;             // W^T fragments of dx from LDS (VGPR budget)
-  static constexpr int ZS = 2 * 16 * (4 * H + CHAINB_ZPAD) * 2;
-  static constexpr int DH = 2 * 16 * TMC<H>::HP * 4;
+// H = 16 stages (chain_bwd_stage16): the dz and dh double buffers and the dx wave's dx tiles
+template <int KX>
+struct ChainBLds16 {
+  static constexpr int ZS = 2 * 16 * (4 * 16 + CHAINB_ZPAD) * 2;
+  static constexpr int DH = 2 * 16 * TMC<16>::HP * 4;
   static constexpr int DX = 2 * 16 * (32 * KX + CHAINB_XPAD) * 4;
-  static constexpr int WB = WL ? 2 * KX * 16 * (4 * H + 8) * 2 : 0;
-  static constexpr int BYTES = ZS + DH + DX + WB;
+  static constexpr int BYTES = ZS + DH + DX;
 };
-// H >= 32 stages split the two per-step products over K (chain_bwd_stage, SK): every wave runs a
+// H >= 32 stages split the two per-step products over K (chain_bwd_stage_sk): every wave runs a
 // full 16-row MFMA tile of dh_rec^T = U dz^T / dx^T = W dz^T over a K slice and the partial tiles
 // meet in LDS (dpart / xpart, a second barrier per step). The one-tile-per-wave layout (each wave
 // owning its own four units: 12 of every 16 A rows zero) issued 4x the MFMAs and made those stages
@@ -1109,8 +1083,9 @@ struct ChainBLdsSK {
 };
 constexpr int chainb_max(int a, int b) { return a > b ? a : b; }
 static constexpr int CHAINB_LDS_STAGE =
-    chainb_max(chainb_max(ChainBLds<64, 2>::BYTES, ChainBLdsSK<64, 1>::BYTES),
-               chainb_max(ChainBLdsSK<64, 2>::BYTES, chainb_max(ChainBLdsSK<32, 1>::BYTES, ChainBLdsSK<32, 2>::BYTES)));
+    chainb_max(chainb_max(ChainBLds16<1>::BYTES, ChainBLds16<2>::BYTES),
+               chainb_max(chainb_max(ChainBLdsSK<32, 1>::BYTES, ChainBLdsSK<32, 2>::BYTES),
+                          chainb_max(ChainBLdsSK<64, 1>::BYTES, ChainBLdsSK<64, 2>::BYTES)));
 
 struct ChainT4BLds {
   static constexpr int DHT = 16 * 132 * 4;                 // dh_{T-1} from the head
@@ -1126,15 +1101,6 @@ static constexpr int CHAINB_LDS = ChainT4BLds::BYTES > CHAINB_LDS_STAGE ? ChainT
 #ifndef CHAINB_LEAD
 #define CHAINB_LEAD 1
 #endif
-#ifndef CHAINB_IO
-#define CHAINB_IO 0          // 1: H = 16 stages as compute / rotating I/O / publisher waves (chain_bwd_stage_io);
-                             // measured slower (bottom stages end 123 / 140 vs 113 / 117 us, bench 0.307 vs
-                             // 0.286 ms/step): the I/O waves' staging and load issue hold up the step barrier
-#endif
-#ifndef CHAINB_DXW
-#define CHAINB_DXW 1         // H = 16 stages: dx = W dz by a dedicated wave (not by compute waves 0 / 1 between
-                             // the step's MFMA and the next cell phase, which put it on the recurrence's path)
-#endif
 #ifndef CHAINB_PUBBATCH
 #define CHAINB_PUBBATCH 4    // backward publisher: LDS reads of this many dx elements per lane, then their stores
 #endif
@@ -1148,16 +1114,6 @@ static constexpr int CHAINB_LDS = ChainT4BLds::BYTES > CHAINB_LDS_STAGE ? ChainT
 #ifndef CHAINB_DXPRIO
 #define CHAINB_DXPRIO 2      // s_setprio of the backward dx wave (same-box A/B: chain bwd 124.0 -> 122.2 us, bench 0.2589 -> 0.2562 ms)
 #endif
-#ifndef CHAINB_PUNPOOL
-#define CHAINB_PUNPOOL 0     // 1: producer-side un-pooling (ChainBStage::uidx). Off: against the round-5 baseline
-                             // build on one box it measured chain bwd 121.4 (on) / 123.9 (compiled in, off) vs 115.9 us
-#endif
-#ifndef CHAINB_DZW
-#define CHAINB_DZW 1         // 1: a dz wave stores each step's dz tile (else the publisher wave does)
-#endif
-#ifndef CHAINB_G
-#define CHAINB_G 2           // waves per backward I/O group: 2 = one for the cell records, one for dh
-#endif
 // ring depths (reverse steps of prefetch) per hidden size
 #ifndef CHAINB_D16
 #define CHAINB_D16 4
@@ -1168,190 +1124,178 @@ static constexpr int CHAINB_LDS = ChainT4BLds::BYTES > CHAINB_LDS_STAGE ? ChainT
 #ifndef CHAINB_D64
 #define CHAINB_D64 2
 #endif
-// threads of a backward stage workgroup: compute waves (+ the publisher wave when it fits, + the dx
-// wave of the split-free H = 16 stages)
+// Threads of a backward stage workgroup. Behind the 16 H / 64 compute waves an H <= 32 stage runs
+// CHAINB_NPUB publisher waves and, last, the dz wave; an H = 16 stage has the dx wave between them.
+// The compute waves of an H = 64 stage fill the workgroup: they store dz and dx themselves.
+// (These helpers keep their general form: the kernel calls chainb_live_threads out of line, so a
+// simpler body would change the device code.)
 __host__ __device__ constexpr bool chainb_dxw(int h) {
-  return CHAINB_DXW && h < 32 && TMC<16>::NT + 64 * CHAINB_NPUB + 64 <= 1024;
+  return h < 32 && TMC<16>::NT + 64 * CHAINB_NPUB + 64 <= 1024;
 }
-// (+ the dz wave: the step's dz tile leaves from its own wave, beside the publisher's dx granules)
-// publisher waves of a stage (0: H = 64, whose compute waves fill the workgroup)
+// publisher waves of a stage (0: H = 64)
 __host__ __device__ constexpr int chainb_npub(int h, int nt) {
   return nt + 64 > 1024 ? 0
        : chainb_max(1, CHAINB_NPUB < (1024 - nt - (chainb_dxw(h) ? 64 : 0) - 64) / 64
                            ? CHAINB_NPUB : (1024 - nt - (chainb_dxw(h) ? 64 : 0) - 64) / 64);
 }
 __host__ __device__ constexpr bool chainb_dzw(int h, int nt) {
-  return CHAINB_DZW && chainb_npub(h, nt) > 0 && nt + 64 * chainb_npub(h, nt) + 64 + (chainb_dxw(h) ? 64 : 0) <= 1024;
+  return chainb_npub(h, nt) > 0 && nt + 64 * chainb_npub(h, nt) + 64 + (chainb_dxw(h) ? 64 : 0) <= 1024;
 }
 __host__ __device__ constexpr int chainb_live_threads(int h, int nt) {
   return nt + 64 * chainb_npub(h, nt) + (chainb_dxw(h) ? 64 : 0) + (chainb_dzw(h, nt) ? 64 : 0);
 }
+static_assert(chainb_dxw(16) && chainb_dzw(16, TMC<16>::NT) && chainb_npub(16, TMC<16>::NT) == CHAINB_NPUB &&
+                  !chainb_dxw(32) && chainb_dzw(32, TMC<32>::NT) && chainb_npub(32, TMC<32>::NT) == CHAINB_NPUB &&
+                  chainb_live_threads(64, TMC<64>::NT) == 1024,
+              "wave roles of the backward stages (chain_bwd_stage16, chain_bwd_stage_sk)");
 
-// lstm_tm_bwd_body (DZ + DX) with one dh element per lane from the stage above's stream
-// (or, stage 0, from global memory), un-pooled on load, and dx published element-wise.
-template <int H, int KX, int D, bool SRC, bool UP, bool XO>
-__device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, int ntiles, int Mp, unsigned tagb,
-                                                int* ctl, char* smem) {
+// One H = 16 layer of one tile, reverse in time: lstm_tm_bwd_body (DZ + DX) with one dh element per
+// lane from the stage above's stream (or, stage 0, from global memory), un-pooled on load, and dx
+// published element-wise.
+//
+// The bottom layers' T reverse steps are the backward's critical path, so between two barriers only
+// what needs dh_rec stays behind the MFMAs, and the hand-off staging runs while LDS reads fly:
+//
+//   barrier s                      dz(s) is in zs[s & 1], dh(s + 1) in dhs[(s + 1) & 1]
+//   ds_read_b128 of dz(s) K-block 0, MFMA as soon as it is there
+//   ds_read_b128 of K-block 1 and the read of dh(s + 1)
+//     while they fly: dh(s + 2) from its ring slot (tag check, un-pool select) -> dhs[s & 1],
+//                     ring load of dh(s + 2 + D)
+//   second MFMA: dh_rec = U dz(s)
+//     in its shadow: gates of step s + 1 unpacked, tanh(c), every factor that does not need dh_rec
+//   dh = dh(s + 1) + dh_rec, dct, dc, four products, bf16, dz(s + 1) -> zs[(s + 1) & 1]
+//   state load of step s + 1 + D into the slot just consumed
+//
+// dhs[s & 1] was last read after barrier s - 1 and is read again after barrier s + 1, so two
+// buffers suffice. Steps past the sequence (s >= T, and the un-pooling tail past the last pooling
+// window) carry no source granule: they are never waited for and stage a zero. The hoisted
+// factors reassociate the cell's products (dct * (g * i * (1 - i)) for ((dct * g) * i) * (1 - i)):
+// bf16 rounding flips in dz against the per-layer kernels, nothing else.
+// Measured placements (profiles/chain_bwd_h16_pipeline_ab.txt): both K-block reads ahead of the
+// first MFMA, tanh(c) ahead of the MFMAs, the state load pinned behind the dz stores or moved into
+// the MFMA shadow, chain_wait inlined, a ring of 2 / 3 / 5 / 6 steps: all slower than this order.
+// Wave-uniform cursors replace the per-step address products: the saved state and the dh source
+// are walked one step at a time, and every load is a fixed base, a 32-bit step offset and a lane
+// offset (the arrays of an H = 16 stage stay below 4 GiB: lstm_chain_bwd checks it).
+//
+// dx^T = W dz^T is the dx wave's, not the compute waves' (between the step's MFMA and the next cell
+// phase it sat on the recurrence's path).
+template <int KX, int D, bool SRC, bool UP, bool XO>
+__device__ __forceinline__ void chain_bwd_stage16(const ChainBStage S, int tile, int ntiles, int Mp, unsigned tagb,
+                                                  int* ctl, char* smem) {
+  constexpr int H = 16;
   using C = TMC<H>;
-  constexpr int CPL = C::CPL, NW = C::NW, NT = C::NT, G4 = C::G4, KB = C::KB;
+  constexpr int NW = C::NW, NT = C::NT, G4 = C::G4, KB = C::KB;
   constexpr int NXB = KX * 2;
-  constexpr int TX = (NXB + NW - 1) / NW;
-  constexpr bool SK = H >= 32;                     // split-K products (ChainBLdsSK)
-  static_assert(CPL == 1 && 16 * H == NT, "one dh element per lane");
-  using L = ChainBLds<H, KX>;
-  using LK = ChainBLdsSK<H, KX>;
-  constexpr int UT = LK::UT, KG = LK::KG, KXG = LK::KXG, KPG = SK ? KB / KG : 1, KPX = SK ? KB / KXG : 1;
-  static_assert(!SK || (NW % UT == 0 && KB % KG == 0 && NW % NXB == 0 && KB % KXG == 0), "split-K tiling");
-  static_assert(L::BYTES <= CHAINB_LDS_STAGE && LK::BYTES <= CHAINB_LDS_STAGE && L::ZS % 16 == 0 && L::DH % 16 == 0,
-                "chain bwd LDS layout");
+  constexpr int NPUB = CHAINB_NPUB;
+  static_assert(C::CPL == 1 && 16 * H == NT && KB == 2, "one dh element per lane, two K blocks of dz");
+  static_assert(D >= 2, "H = 16 stage: ring of at least two steps");
+  using L = ChainBLds16<KX>;
+  static_assert(L::BYTES <= CHAINB_LDS_STAGE && L::ZS % 16 == 0 && L::DH % 16 == 0, "chain bwd LDS layout");
   auto zs = reinterpret_cast<__bf16 (*)[16][G4 + CHAINB_ZPAD]>(smem);
-  // dz element e of sequence c at zs[.][c][chz(c, e)]: 16-byte chunk XOR bit 2 of the sequence (as lstm_tm.hip)
-  auto chz = [](int c, int e) { return CHAINB_ZSWZ ? e ^ (((c >> 2) & 1) << 3) : e; };
   auto dhs = reinterpret_cast<float (*)[16][C::HP]>(smem + L::ZS);
   auto dxs = reinterpret_cast<float (*)[16][32 * KX + CHAINB_XPAD]>(smem + L::ZS + L::DH);
-  auto wl = reinterpret_cast<__bf16 (*)[16][G4 + 8]>(smem + L::ZS + L::DH + L::DX);
-  auto dpart = reinterpret_cast<float (*)[16][C::HP]>(smem + LK::ZS + LK::DH);                      // [KG]
-  auto xpart = reinterpret_cast<float (*)[KXG][16][LK::XPP]>(smem + LK::ZS + LK::DH + LK::DP);      // [2][KXG]
 
   const int T = S.T, Din = S.Din, Dw = S.Dw, P = S.P, Ts = S.Ts;
   // source kind and un-pooling are template parameters: with run-time branches around the
   // ring loads the compiler drained the whole prefetch ring (vmcnt(0)) every D steps
   const int tid = threadIdx.x, lane = tid & 63;
-  // Publisher wave (a spare wave of the 1024-thread workgroup, H < 64): it alone stores the
-  // dx granules. The write-through (sc1) stores are acknowledged only after the memory
-  // round trip and the vector-memory counter retires in order, so in a compute wave every
-  // wait for a ring load also waited for the stores issued before it (~2 us per step, 6x the
-  // step time). The publisher joins the same barriers and reads the dx tile from LDS.
   const int row0 = tile * 16;
-  constexpr bool PUBW = NT + 64 <= 1024;
-  constexpr int NPUB = chainb_npub(H, NT);
-  constexpr bool DXW = !SK && chainb_dxw(H);
-  constexpr bool DZW = PUBW && chainb_dzw(H, NT);
-  static_assert(PUBW == (NPUB > 0), "publisher waves");
-  static_assert(!DXW || PUBW, "the dx wave hands its tiles to the publisher");
-  if constexpr (DZW) {
-    // dz wave: after step s's barrier (the second one of the step, SK: its first), the dz tile of step s
-    // from zs[s & 1] (held until step s + 2's cell phase) -> HBM with 16-byte stores
-    if (tid >= NT + 64 * NPUB + (DXW ? 64 : 0)) {
-      if (CHAINB_PUBPRIO > 0) __builtin_amdgcn_s_setprio(CHAINB_PUBPRIO);
-      const int nsteps = (T + D - 1) / D * D;
-      __syncthreads();
-      __syncthreads();
-      for (int s = 0; s < nsteps; ++s) {
-        lds_barrier();
-        if (s < T) {
-          const int pb = s & 1;
-          __bf16* zt = S.dz + ((size_t)(T - 1 - s) * Mp + row0) * G4;
+  if (tid >= NT + 64 * NPUB + 64) {
+    // dz wave: after step s's barrier, the dz tile of step s from zs[s & 1] (held until step s + 2's
+    // cell phase) -> HBM with 16-byte stores, beside the publisher's dx granules
+    if (CHAINB_PUBPRIO > 0) __builtin_amdgcn_s_setprio(CHAINB_PUBPRIO);
+    const int nsteps = (T + D - 1) / D * D;
+    __syncthreads();
+    __syncthreads();
+    for (int s = 0; s < nsteps; ++s) {
+      lds_barrier();
+      if (s < T) {
+        const int pb = s & 1;
+        __bf16* zt = S.dz + ((size_t)(T - 1 - s) * Mp + row0) * G4;
 #pragma unroll
-          for (int q = lane; q < 16 * G4 / 8; q += 64) {
-            const int e = 8 * q;
-            *reinterpret_cast<uint4*>(zt + e) = *reinterpret_cast<const uint4*>(&zs[pb][e / G4][chz(e / G4, e % G4)]);
-          }
+        for (int q = lane; q < 16 * G4 / 8; q += 64) {
+          const int e = 8 * q;
+          *reinterpret_cast<uint4*>(zt + e) = *reinterpret_cast<const uint4*>(&zs[pb][e / G4][e % G4]);
         }
-        if constexpr (SK) lds_barrier();
       }
-      __syncthreads();
-      return;
     }
+    __syncthreads();
+    return;
   }
-  if constexpr (DXW) {
+  if (tid >= NT + 64 * NPUB) {
     // dx wave: after step s's barrier, dx^T = W dz^T of that step from zs[s & 1] into dxs[s & 1]
-    // (the publisher stores it after the next barrier, as before). It joins barrier s + 1 only once
+    // (the publisher stores it after the next barrier). It joins barrier s + 1 only once
     // done, and zs[s & 1] is rewritten only in step s + 2's cell phase (after barrier s + 1), so the
     // compute waves go from their dh_rec MFMA straight to the next cell phase.
-    if (tid >= NT + 64 * NPUB) {
-      if (CHAINB_DXPRIO > 0) __builtin_amdgcn_s_setprio(CHAINB_DXPRIO);
-      const int col = lane & 15, quad = lane >> 4;
-      bf16x8_t wx[NXB][KB];
+    if (CHAINB_DXPRIO > 0) __builtin_amdgcn_s_setprio(CHAINB_DXPRIO);
+    const int col = lane & 15, quad = lane >> 4;
+    bf16x8_t wx[NXB][KB];
 #pragma unroll
-      for (int xb = 0; xb < NXB; ++xb) {
-        const int din = 16 * xb + col;
+    for (int xb = 0; xb < NXB; ++xb) {
+      const int din = 16 * xb + col;
 #pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          bf16x8_t v;
+      for (int k = 0; k < KB; ++k) {
+        bf16x8_t v;
 #pragma unroll
-          for (int j = 0; j < 8; ++j)
-            v[j] = (__bf16)(S.W[(size_t)min(din, Dw - 1) * G4 + 32 * k + 8 * quad + j] * (din < Dw ? 1.f : 0.f));
-          wx[xb][k] = v;
-        }
+        for (int j = 0; j < 8; ++j)
+          v[j] = (__bf16)(S.W[(size_t)min(din, Dw - 1) * G4 + 32 * k + 8 * quad + j] * (din < Dw ? 1.f : 0.f));
+        wx[xb][k] = v;
       }
-      const int nsteps = (T + D - 1) / D * D;
-      __syncthreads();
-      __syncthreads();
-      for (int s = 0; s < nsteps; ++s) {
-        lds_barrier();
-        if (s < T) {
-          const int p = s & 1;
-          bf16x8_t bz[KB];
-#pragma unroll
-          for (int k = 0; k < KB; ++k) bz[k] = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 * k + 8 * quad)]);
-#pragma unroll
-          for (int xb = 0; xb < NXB; ++xb) {
-            f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < KB; ++k) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wx[xb][k], bz[k], a, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dxs[p][col][16 * xb + 4 * quad + r] = a[r];
-          }
-          chain_mark_wave((S.prof != nullptr && tile == 0) ? S.prof : nullptr, s, 6);   // (dx tile in LDS)
-        }
-      }
-      __syncthreads();
-      return;
     }
-  }
-  if constexpr (PUBW) {
-    if (tid >= NT) {
-      if (CHAINB_PUBPRIO > 0) __builtin_amdgcn_s_setprio(CHAINB_PUBPRIO);
-      const int nsteps = (T + D - 1) / D * D;
-      const int nx = 16 * Din;
-      const size_t xstep = (size_t)Mp * Din;
-      // publisher wave pj of NPUB publishes the 64-element slices pj, pj + NPUB, ... of each dx tile
-      const int pj = (tid - NT) >> 6;
-      constexpr int ESTR = 64 * (NPUB > 0 ? NPUB : 1);
-      const int dq = ESTR / Din, dr = ESTR % Din;
-      // producer-side un-pooling: this tile's argmax bytes of all T steps in LDS (loaded before the
-      // publisher's first store, so no load of it waits behind its write-through stores), and the
-      // full-resolution steps past the last pooling window published as zeros up front (the stage
-      // below needs them first)
-      constexpr int UPOFF = ((SK ? LK::BYTES : L::BYTES) + 15) / 16 * 16;
-      unsigned char* ub = reinterpret_cast<unsigned char*>(smem + UPOFF);
-      const bool unp = CHAINB_PUNPOOL && XO && S.uidx != nullptr;
-      if (unp) {
-        const int nw4 = T * 16 * Din / 4;
-        for (int i = tid - NT; i < nw4; i += ESTR) {
-          const int e = 4 * i, ts = e / (16 * Din), r = e % (16 * Din);
-          *reinterpret_cast<unsigned*>(ub + e) =
-              *reinterpret_cast<const unsigned*>(S.uidx + ((size_t)ts * Mp + row0) * Din + r);
+    const int nsteps = (T + D - 1) / D * D;
+    __syncthreads();
+    __syncthreads();
+    for (int s = 0; s < nsteps; ++s) {
+      lds_barrier();
+      if (s < T) {
+        const int p = s & 1;
+        bf16x8_t bz[KB];
+#pragma unroll
+        for (int k = 0; k < KB; ++k) bz[k] = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][32 * k + 8 * quad]);
+#pragma unroll
+        for (int xb = 0; xb < NXB; ++xb) {
+          f32x4_t a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int k = 0; k < KB; ++k) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wx[xb][k], bz[k], a, 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dxs[p][col][16 * xb + 4 * quad + r] = a[r];
         }
-        for (int tt = T * S.uP; tt < S.uT; ++tt)
-          for (int e = tid - NT; e < nx; e += ESTR)
-            st_granule(S.sout + (size_t)row0 * Din + e + (size_t)tt * xstep, 0.f, tagb | (unsigned)tt);
+        chain_mark_wave((S.prof != nullptr && tile == 0) ? S.prof : nullptr, s, 6);   // (dx tile in LDS)
       }
-      // LDS reads of CHAINB_PUBBATCH elements per lane first, then their stores: a read -> wait -> store
-      // loop per element paid one LDS round trip per element on the publisher's step (16 Din / 64 =
-      // Din / 4 elements per lane, the same count on every lane since Din % 4 == 0). (All Din / 4 at
-      // once, up to 16, pushed the kernel from 32 to 176 bytes of scratch: chain bwd 133 -> 258 us.)
-      constexpr int PUBN = CHAINB_PUBBATCH > 0 ? CHAINB_PUBBATCH : 1;   // elements per lane per batch
-      auto publish = [&](int buf, int ts) {
-        const unsigned tag = tagb | (unsigned)ts;
-        for (int e0 = 64 * pj; e0 < nx; e0 += ESTR * PUBN) {
+    }
+    __syncthreads();
+    return;
+  }
+  if (tid >= NT) {
+    // Publisher waves (spare waves of the 1024-thread workgroup): they alone store the dx granules.
+    // The write-through (sc1) stores are acknowledged only after the memory round trip and the
+    // vector-memory counter retires in order, so in a compute wave every wait for a ring load also
+    // waited for the stores issued before it (~2 us per step, 6x the step time). The publishers join
+    // the same barriers and read the dx tile from LDS.
+    if (CHAINB_PUBPRIO > 0) __builtin_amdgcn_s_setprio(CHAINB_PUBPRIO);
+    const int nsteps = (T + D - 1) / D * D;
+    const int nx = 16 * Din;
+    const size_t xstep = (size_t)Mp * Din;
+    // publisher wave pj of NPUB publishes the 64-element slices pj, pj + NPUB, ... of each dx tile
+    const int pj = (tid - NT) >> 6;
+    constexpr int ESTR = 64 * NPUB;
+    const int dq = ESTR / Din, dr = ESTR % Din;
+    // LDS reads of CHAINB_PUBBATCH elements per lane first, then their stores: a read -> wait -> store
+    // loop per element paid one LDS round trip per element on the publisher's step (16 Din / 64 =
+    // Din / 4 elements per lane, the same count on every lane since Din % 4 == 0). (All Din / 4 at
+    // once, up to 16, pushed the kernel from 32 to 176 bytes of scratch: chain bwd 133 -> 258 us.)
+    constexpr int PUBN = CHAINB_PUBBATCH > 0 ? CHAINB_PUBBATCH : 1;   // elements per lane per batch
+    auto publish = [&](int buf, int ts) {
+      const unsigned tag = tagb | (unsigned)ts;
+      for (int e0 = 64 * pj; e0 < nx; e0 += ESTR * PUBN) {
         const int niter = min((nx - e0 + ESTR - 1) / ESTR, PUBN);
         float vv[PUBN];
-        unsigned bb[PUBN];
         int row = (lane + e0) / Din, k = (lane + e0) % Din;
 #pragma unroll
         for (int i = 0; i < PUBN; ++i) {
           if (i < niter) {                          // wave-uniform
-            if constexpr (SK) {
-              float v = 0.f;
-#pragma unroll
-              for (int g = 0; g < KXG; ++g) v += xpart[buf][g][row][k];
-              vv[i] = v;
-            } else {
-              vv[i] = dxs[buf][row][k];
-            }
-            bb[i] = unp ? (unsigned)ub[(ts * 16 + row) * Din + k] : 0u;
+            vv[i] = dxs[buf][row][k];
           }
           row += dq;
           k += dr;
@@ -1361,86 +1305,36 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
         for (int i = 0; i < PUBN; ++i) {
           if (i < niter) {
             const int e = e0 + lane + ESTR * i;
-            if (unp) {
-              for (int qq = 0; qq < S.uP; ++qq) {
-                const int tt = ts * S.uP + qq;
-                st_granule(S.sout + (size_t)row0 * Din + e + (size_t)tt * xstep, bb[i] == (unsigned)qq ? vv[i] : 0.f,
-                           tagb | (unsigned)tt);
-              }
-            } else {
-              const size_t o = (size_t)row0 * Din + e + (size_t)ts * xstep;
-              if constexpr (XO) st_granule(S.sout + o, vv[i], tag);
-              else S.dx[o] = vv[i];
-            }
+            const size_t o = (size_t)row0 * Din + e + (size_t)ts * xstep;
+            if constexpr (XO) st_granule(S.sout + o, vv[i], tag);
+            else S.dx[o] = vv[i];
           }
         }
-        }
-      };
-      // ... and the step's dz tile (16-byte stores from LDS; zs[s & 1] holds it from the barrier
-      // that follows step s's cell phase until the cell phase of step s + 2): the compute waves then
-      // issue only loads, so their waits are for their own loads alone
-      auto store_dz = [&](int ss) {
-        const int pb = ss & 1;
-        __bf16* zt = S.dz + ((size_t)(T - 1 - ss) * Mp + row0) * G4;
-#pragma unroll
-        for (int q = lane; q < 16 * G4 / 8; q += 64) {
-          const int e = 8 * q;
-          *reinterpret_cast<uint4*>(zt + e) = *reinterpret_cast<const uint4*>(&zs[pb][e / G4][chz(e / G4, e % G4)]);
-        }
-      };
-      __syncthreads();
-      __syncthreads();
-      if constexpr (SK) {            // two barriers per step; step s's dx tile is complete after the second
-        for (int s = 0; s < nsteps; ++s) {
-          lds_barrier();
-          if (!DZW && s < T) store_dz(s);
-          lds_barrier();
-          if (s < T) publish(s & 1, T - 1 - s);
-        }
-        __syncthreads();
-      } else {
-        long long* prw = (S.prof != nullptr && tile == 0 && pj == 0) ? S.prof : nullptr;
-        for (int s = 0; s < nsteps; ++s) {
-          lds_barrier();
-          const int t = T - 1 - s;
-          if (!DZW && s < T) store_dz(s);
-          if (s >= 1 && s <= T) publish((s - 1) & 1, t + 1);
-          if (s < T) chain_mark_wave(prw, s, 7);   // (the publisher's work of the step is issued)
-        }
-        __syncthreads();
-        publish((T - 1) & 1, 0);
       }
-      return;
+    };
+    __syncthreads();
+    __syncthreads();
+    long long* prw = (S.prof != nullptr && tile == 0 && pj == 0) ? S.prof : nullptr;
+    for (int s = 0; s < nsteps; ++s) {   // step s - 1's dx tile (the dx wave's) is complete after barrier s
+      lds_barrier();
+      const int t = T - 1 - s;
+      if (s >= 1 && s <= T) publish((s - 1) & 1, t + 1);
+      if (s < T) chain_mark_wave(prw, s, 7);   // (the publisher's work of the step is issued)
     }
+    __syncthreads();
+    publish((T - 1) & 1, 0);
+    return;
   }
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 15, quad = lane >> 4;
 
   for (int i = tid; i < 2 * 16 * C::HP; i += NT) (&dhs[0][0][0])[i] = 0.f;
 
+  // U^T rows of this wave's four units (rows with (col & 3) != 0 zero: element 0 of the product is
+  // this lane's unit)
   const int unit = 4 * w + quad;
-  // SK: wave w owns unit tile ut over K slice kg of dh_rec^T, din tile xt over K slice kx of dx^T
-  const int ut = w % UT, kg = w / UT, xt = w % NXB, kx = w / NXB;
-  bf16x8_t ufr[SK ? KPG : KB];
-  bf16x8_t ufk[SK ? KPX : 1];                      // (SK: the W fragments of this wave's dx slice)
-  if constexpr (SK) {
-#pragma unroll
-    for (int q = 0; q < KPG; ++q) {
-      bf16x8_t v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (__bf16)S.U[(size_t)(16 * ut + col) * G4 + 32 * (kg * KPG + q) + 8 * quad + j];
-      ufr[q] = v;
-    }
-    const int din = 16 * xt + col;
-#pragma unroll
-    for (int q = 0; q < KPX; ++q) {
-      bf16x8_t v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        v[j] = (__bf16)(S.W[(size_t)min(din, Dw - 1) * G4 + 32 * (kx * KPX + q) + 8 * quad + j] * (din < Dw ? 1.f : 0.f));
-      ufk[q] = v;
-    }
-  } else {
+  bf16x8_t ufr[KB];
+  {
     const int au = 4 * w + (col >> 2);
 #pragma unroll
     for (int s = 0; s < KB; ++s) {
@@ -1453,31 +1347,304 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
       ufr[s] = v;
     }
   }
-  bf16x8_t wfr[(L::WL || SK || DXW) ? 1 : TX][(L::WL || SK || DXW) ? 1 : KB];
-  if constexpr (SK || DXW) {
-  } else if constexpr (L::WL) {     // W^T blocks [NXB][16 din][4H] in LDS (unrolled: all loads in flight)
-    static_assert((NXB * 16 * G4) % NT == 0, "W staging trip count");
-#pragma unroll
-    for (int it = 0; it < NXB * 16 * G4 / NT; ++it) {
-      const int i = tid + it * NT;
-      const int xb = i / (16 * G4), r = (i / G4) % 16, k = i % G4;
-      const int din = 16 * xb + r;
-      wl[xb][r][k] = (__bf16)(S.W[(size_t)min(din, Dw - 1) * G4 + k] * (din < Dw ? 1.f : 0.f));   // no branch
+
+  // forward state ring (gates, c_t) and the dh element ring, D reverse steps ahead
+  uint2 rg[D];                       // packed bf16 gates
+  float rc[D];
+  unsigned long long rq[D];
+  unsigned ri[D];
+  // tt / P as a multiply-high with the magic floor(2^32 / P) + 1 (exact for tt * P < 2^32; here
+  // tt < 4096, P <= 255): the per-step integer divisions by the run-time pool size cost the
+  // un-pooling stages ~160 shader clocks per step on the dh staging (phase table, round 5). The
+  // magic of P == 1 would be 2^32, which wraps to 0, so that pool size (a chain that ends in
+  // MaxPooling1D(1)) takes the identity instead
+  const unsigned pmag = (UP && P > 1) ? 0xFFFFFFFFu / (unsigned)P + 1u : 0u;
+  auto divp = [&](int tt) { return P > 1 ? (int)__umulhi((unsigned)tt, pmag) : tt; };
+  // source time of the dh of time tt (-1: past the last pooling window -> zero gradient)
+  auto src_t = [&](int tt) {
+    if constexpr (UP) return tt < Ts * P ? divp(tt) : -1;
+    else return tt;
+  };
+  const size_t eoff = (size_t)row0 * H + tid;        // this lane's dh element in a [Mp][H] row block
+  const size_t hstep = (size_t)Mp * H;
+
+  if constexpr (SRC) {    // start once the stage above is D + LEAD steps ahead (see the forward)
+    int tw = T - 1 - (D + CHAINB_LEAD);
+    tw = max(tw, 0);
+    const int st = src_t(tw);
+    if (st >= 0) (void)chain_wait(S.din + eoff + (size_t)st * hstep, tagb | (unsigned)st, ctl);
+  }
+  constexpr unsigned NOSRC = 0xFFFFFFFFu;
+  const unsigned lo8 = (unsigned)((tile * NW + w) * 64 + lane) * 8u;    // this lane's cell in a state step (bytes of g)
+  const unsigned gstr = (unsigned)(ntiles * NW * 64 * 8);               // bytes per step of g (c: half)
+  const char* gbase = reinterpret_cast<const char*>(S.g);
+  const char* cbase = reinterpret_cast<const char*>(S.c);
+  int stt = T - 1;                                                      // time of the next state load
+  auto state_load = [&](int J) {
+    const unsigned o = (unsigned)__builtin_amdgcn_readfirstlane(stt) * gstr + lo8;   // (a scalar product)
+    rg[J] = *reinterpret_cast<const uint2*>(gbase + o);
+    rc[J] = *reinterpret_cast<const float*>(cbase + (o >> 1));
+    stt = max(stt - 1, 0);                                              // (steps past the sequence reload t = 0)
+  };
+  // dh source cursor: time dtt (< 0 past the sequence), source row dst and phase dph = dtt - dst P of
+  // an un-pooling stage (dph >= P: the tail past the last pooling window, read from the last row)
+  constexpr unsigned ESZ = SRC ? 8 : 4;
+  const unsigned eo = (unsigned)eoff;
+  const unsigned hrow = (unsigned)hstep;
+  const char* dbase = SRC ? reinterpret_cast<const char*>(S.din) : reinterpret_cast<const char*>(S.dh);
+  const char* pbase = reinterpret_cast<const char*>(S.pidx);
+  int dtt = T - 1;
+  int dst = UP ? min(divp(dtt), Ts - 1) : dtt;
+  int dph = UP ? dtt - dst * P : 0;
+  const unsigned dlim = (unsigned)(UP ? Ts * P : T);                    // times with a source granule: [0, dlim)
+  unsigned rinf[D];                 // per ring slot: phase << 12 | source row, NOSRC: no source granule
+  auto ring_load = [&](int J) {
+    const unsigned o = (unsigned)max(dst, 0) * hrow + eo;
+    if constexpr (SRC) rq[J] = ld_granule(reinterpret_cast<const unsigned long long*>(dbase + o * ESZ));
+    else rq[J] = (unsigned long long)__float_as_uint(*reinterpret_cast<const float*>(dbase + o * ESZ));
+    if constexpr (UP) ri[J] = (unsigned)*reinterpret_cast<const unsigned char*>(pbase + o);
+    else ri[J] = 0u;
+    const unsigned inf = ((unsigned)dph << 12) | (unsigned)dst;
+    rinf[J] = (unsigned)dtt < dlim ? inf : NOSRC;
+    --dtt;
+    if constexpr (UP) {
+      const bool wrap = dph == 0;                                       // the source row changes
+      dst = wrap ? dst - 1 : dst;
+      dph = wrap ? P - 1 : dph - 1;
+    } else {
+      --dst;
     }
-  } else {
-#pragma unroll
-    for (int q = 0; q < TX; ++q) {
-      const int xb = w + NW * q;
-      const int din = 16 * xb + col;
-#pragma unroll
-      for (int s = 0; s < KB; ++s) {
-        bf16x8_t v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          v[j] = (__bf16)(S.W[(size_t)min(din, Dw - 1) * G4 + 32 * s + 8 * quad + j] *
-                          ((xb < NXB && din < Dw) ? 1.f : 0.f));
-        wfr[q][s] = v;
+  };
+  // dh of ring slot J (tag-checked for a stream source, un-pool select)
+  auto stage = [&](int J) -> float {
+    const unsigned inf = rinf[J];
+    const bool has = inf != NOSRC;
+    if constexpr (SRC) {
+      const unsigned want = tagb | (inf & 0xfffu);
+      const bool bad = has && (unsigned)(rq[J] >> 32) != want;
+      if (__builtin_amdgcn_ballot_w64(bad) != 0) {
+        rq[J] = chain_wait(S.din + eoff + (size_t)(inf & 0xfffu) * hstep, want, ctl);
       }
+    }
+    const float v = __uint_as_float((unsigned)rq[J]);
+    bool keep = has;
+    if constexpr (UP) keep = keep && ri[J] == (inf >> 12);
+    return keep ? v : 0.f;
+  };
+  // the cell of one step in two halves: what the saved state alone gives, and what needs dh_rec
+  // (tanh(c) stays a statement of its own: folded into cell_pre as a local the compiler scheduled the
+  // step differently, same-box 0.2383-0.2403 against 0.2350-0.2360 ms/step)
+  float tc, fo, ff, z0, z1, z2, z3;
+  auto cell_pre_c = [&](int J) { tc = tanhf_fast(rc[J]); };
+  auto cell_pre = [&](int J, int JN, int tt) {
+    const float cp = rc[JN] * (tt > 0 ? 1.f : 0.f);                     // c_{t-1}
+    const float4 g4 = gates_unpack(rg[J]);
+    fo = g4.w * (1.f - tc * tc);
+    ff = g4.y;
+    z0 = g4.z * g4.x * (1.f - g4.x);
+    z1 = cp * g4.y * (1.f - g4.y);
+    z2 = g4.x * (1.f - g4.z * g4.z);
+    z3 = tc * g4.w * (1.f - g4.w);
+  };
+  float dc = 0.f;
+  auto cell_tail = [&](int pb, float dh) {
+    const float dct = dc + dh * fo;
+    dc = dct * ff;
+    zs[pb][col][0 * H + unit] = (__bf16)(dct * z0);
+    zs[pb][col][1 * H + unit] = (__bf16)(dct * z1);
+    zs[pb][col][2 * H + unit] = (__bf16)(dct * z2);
+    zs[pb][col][3 * H + unit] = (__bf16)(dh * z3);
+  };
+
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    state_load(j);
+    ring_load(j);
+  }
+  __syncthreads();
+  dhs[0][tid / H][tid % H] = stage(0);          // dh of steps 0 and 1
+  ring_load(0);
+  dhs[1][tid / H][tid % H] = stage(1);
+  ring_load(1);
+  __syncthreads();
+  float dhn = dhs[0][col][unit];
+  if (tid == 0 && S.trace_mid) S.trace_mid[blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
+  cell_pre_c(0);
+  cell_pre(0, 1, T - 1);                        // step 0: no dh_rec yet
+  cell_tail(0, dhn);
+  state_load(0);
+
+  long long* pr = (S.prof != nullptr && tile == 0) ? S.prof : nullptr;
+  for (int s0 = 0; s0 < T; s0 += D) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      const int s = s0 + j;
+      const int p = s & 1;
+      const int j1 = (j + 1) % D, j2 = (j + 2) % D;
+      lds_barrier();
+      chain_mark(pr, s, 0);
+      const bf16x8_t bz0 = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][8 * quad]);
+      __builtin_amdgcn_sched_barrier(0);         // (the fences keep this order: see the stage's header)
+      f32x4_t a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[0], bz0, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      const bf16x8_t bz1 = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][32 + 8 * quad]);
+      dhn = dhs[p ^ 1][col][unit];
+      dhs[p][tid / H][tid % H] = stage(j2);     // dh of step s + 2, then its slot's next load
+      ring_load(j2);
+      chain_mark(pr, s, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      const f32x4_t a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[1], bz1, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      cell_pre_c(j1);
+      cell_pre(j1, j2, T - 2 - s);
+      __builtin_amdgcn_sched_barrier(0);
+      float dhr = a0[0] + a1[0];
+#ifdef GQ_CHAIN_PROF
+      if (pr != nullptr) asm volatile("" : "+v"(dhr));
+#endif
+      chain_mark(pr, s, 2);
+      cell_tail(p ^ 1, dhn + dhr);
+      chain_mark(pr, s, 3);
+      state_load(j1);
+      chain_mark(pr, s, 4);
+    }
+  }
+  __syncthreads();
+}
+
+// One H = 32 / 64 layer of one tile, reverse in time, with the two per-step products split over K
+// (ChainBLdsSK): the cell phase, a barrier, the partial products into LDS, a second barrier, the sum
+// of the dh_rec partials. dh comes one element per lane from the stage above's stream (or, stage 0,
+// from global memory), un-pooled on load. An H = 32 stage hands its dz and dx tiles to the dz wave
+// and the publisher waves; the compute waves of an H = 64 stage store them themselves.
+template <int H, int KX, int D, bool SRC, bool UP, bool XO>
+__device__ __forceinline__ void chain_bwd_stage_sk(const ChainBStage S, int tile, int ntiles, int Mp, unsigned tagb,
+                                                   int* ctl, char* smem) {
+  using C = TMC<H>;
+  constexpr int CPL = C::CPL, NW = C::NW, NT = C::NT, G4 = C::G4, KB = C::KB;
+  constexpr int NXB = KX * 2;
+  static_assert(H >= 32 && CPL == 1 && 16 * H == NT, "one dh element per lane");
+  using LK = ChainBLdsSK<H, KX>;
+  constexpr int UT = LK::UT, KG = LK::KG, KXG = LK::KXG, KPG = KB / KG, KPX = KB / KXG;
+  constexpr int NPUB = CHAINB_NPUB;
+  static_assert(NW % UT == 0 && KB % KG == 0 && NW % NXB == 0 && KB % KXG == 0, "split-K tiling");
+  static_assert(LK::BYTES <= CHAINB_LDS_STAGE && LK::ZS % 16 == 0 && LK::DH % 16 == 0, "chain bwd LDS layout");
+  auto zs = reinterpret_cast<__bf16 (*)[16][G4 + CHAINB_ZPAD]>(smem);
+  auto dhs = reinterpret_cast<float (*)[16][C::HP]>(smem + LK::ZS);
+  auto dpart = reinterpret_cast<float (*)[16][C::HP]>(smem + LK::ZS + LK::DH);                      // [KG]
+  auto xpart = reinterpret_cast<float (*)[KXG][16][LK::XPP]>(smem + LK::ZS + LK::DH + LK::DP);      // [2][KXG]
+
+  const int T = S.T, Din = S.Din, Dw = S.Dw, P = S.P, Ts = S.Ts;
+  // source kind and un-pooling are template parameters: with run-time branches around the
+  // ring loads the compiler drained the whole prefetch ring (vmcnt(0)) every D steps
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int row0 = tile * 16;
+  constexpr bool PUBW = H == 32;                   // publisher waves and the dz wave (chainb_live_threads)
+  if constexpr (PUBW) {
+    if (tid >= NT + 64 * NPUB) {
+      // dz wave: after step s's barrier (the first of the step's two), the dz tile of step s from zs[s & 1] (held until step s + 2's
+      // cell phase) -> HBM with 16-byte stores, beside the publisher's dx granules
+      if (CHAINB_PUBPRIO > 0) __builtin_amdgcn_s_setprio(CHAINB_PUBPRIO);
+      const int nsteps = (T + D - 1) / D * D;
+      __syncthreads();
+      __syncthreads();
+      for (int s = 0; s < nsteps; ++s) {
+        lds_barrier();
+        if (s < T) {
+          const int pb = s & 1;
+          __bf16* zt = S.dz + ((size_t)(T - 1 - s) * Mp + row0) * G4;
+#pragma unroll
+          for (int q = lane; q < 16 * G4 / 8; q += 64) {
+            const int e = 8 * q;
+            *reinterpret_cast<uint4*>(zt + e) = *reinterpret_cast<const uint4*>(&zs[pb][e / G4][e % G4]);
+          }
+        }
+        lds_barrier();
+      }
+      __syncthreads();
+      return;
+    }
+    if (tid >= NT) {
+      // publisher waves, as in chain_bwd_stage16; the dx tile is the sum of the K slices' partial tiles
+      if (CHAINB_PUBPRIO > 0) __builtin_amdgcn_s_setprio(CHAINB_PUBPRIO);
+      const int nsteps = (T + D - 1) / D * D;
+      const int nx = 16 * Din;
+      const size_t xstep = (size_t)Mp * Din;
+      // publisher wave pj of NPUB publishes the 64-element slices pj, pj + NPUB, ... of each dx tile
+      const int pj = (tid - NT) >> 6;
+      constexpr int ESTR = 64 * NPUB;
+      const int dq = ESTR / Din, dr = ESTR % Din;
+      // LDS reads of CHAINB_PUBBATCH elements per lane first, then their stores: a read -> wait -> store
+      // loop per element paid one LDS round trip per element on the publisher's step (16 Din / 64 =
+      // Din / 4 elements per lane, the same count on every lane since Din % 4 == 0). (All Din / 4 at
+      // once, up to 16, pushed the kernel from 32 to 176 bytes of scratch: chain bwd 133 -> 258 us.)
+      constexpr int PUBN = CHAINB_PUBBATCH > 0 ? CHAINB_PUBBATCH : 1;   // elements per lane per batch
+      auto publish = [&](int buf, int ts) {
+        const unsigned tag = tagb | (unsigned)ts;
+        for (int e0 = 64 * pj; e0 < nx; e0 += ESTR * PUBN) {
+          const int niter = min((nx - e0 + ESTR - 1) / ESTR, PUBN);
+          float vv[PUBN];
+          int row = (lane + e0) / Din, k = (lane + e0) % Din;
+#pragma unroll
+          for (int i = 0; i < PUBN; ++i) {
+            if (i < niter) {                          // wave-uniform
+              float v = 0.f;
+#pragma unroll
+              for (int g = 0; g < KXG; ++g) v += xpart[buf][g][row][k];
+              vv[i] = v;
+            }
+            row += dq;
+            k += dr;
+            if (k >= Din) { k -= Din; ++row; }
+          }
+#pragma unroll
+          for (int i = 0; i < PUBN; ++i) {
+            if (i < niter) {
+              const int e = e0 + lane + ESTR * i;
+              const size_t o = (size_t)row0 * Din + e + (size_t)ts * xstep;
+              if constexpr (XO) st_granule(S.sout + o, vv[i], tag);
+              else S.dx[o] = vv[i];
+            }
+          }
+        }
+      };
+      __syncthreads();
+      __syncthreads();
+      for (int s = 0; s < nsteps; ++s) {   // two barriers per step; step s's dx tile is complete after the second
+        lds_barrier();
+        lds_barrier();
+        if (s < T) publish(s & 1, T - 1 - s);
+      }
+      __syncthreads();
+      return;
+    }
+  }
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 15, quad = lane >> 4;
+
+  for (int i = tid; i < 2 * 16 * C::HP; i += NT) (&dhs[0][0][0])[i] = 0.f;
+
+  const int unit = 4 * w + quad;
+  // wave w owns unit tile ut over K slice kg of dh_rec^T, din tile xt over K slice kx of dx^T
+  const int ut = w % UT, kg = w / UT, xt = w % NXB, kx = w / NXB;
+  bf16x8_t ufr[KPG];
+  bf16x8_t ufk[KPX];                               // (the W fragments of this wave's dx slice)
+#pragma unroll
+  for (int q = 0; q < KPG; ++q) {
+    bf16x8_t v;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (__bf16)S.U[(size_t)(16 * ut + col) * G4 + 32 * (kg * KPG + q) + 8 * quad + j];
+    ufr[q] = v;
+  }
+  {
+    const int din = 16 * xt + col;
+#pragma unroll
+    for (int q = 0; q < KPX; ++q) {
+      bf16x8_t v;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        v[j] = (__bf16)(S.W[(size_t)min(din, Dw - 1) * G4 + 32 * (kx * KPX + q) + 8 * quad + j] * (din < Dw ? 1.f : 0.f));
+      ufk[q] = v;
     }
   }
 
@@ -1487,11 +1654,7 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
   unsigned long long rq[D];
   unsigned ri[D];
   auto sidx = [&](int tt) { return ((((size_t)tt * ntiles + tile) * NW + w)) * 64 + lane; };
-  // tt / P as a multiply-high with the magic floor(2^32 / P) + 1 (exact for tt * P < 2^32; here
-  // tt < 4096, P <= 255): the per-step integer divisions by the run-time pool size cost the
-  // un-pooling stages ~160 shader clocks per step on the dh staging (phase table, round 5)
-  // un-pooling stages; the magic of P == 1 would be 2^32, which wraps to 0, so that pool size
-  // (a chain that ends in MaxPooling1D(1)) takes the identity instead
+  // tt / P as a multiply-high (see chain_bwd_stage16); P == 1 takes the identity
   const unsigned pmag = (UP && P > 1) ? 0xFFFFFFFFu / (unsigned)P + 1u : 0u;
   auto divp = [&](int tt) { return P > 1 ? (int)__umulhi((unsigned)tt, pmag) : tt; };
   // source time of the dh of time tt (-1: past the last pooling window -> zero gradient)
@@ -1528,7 +1691,8 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
     if constexpr (UP) keep = keep && ri[J] == (unsigned)(tt - st * P);
     return keep ? v : 0.f;
   };
-  // dz storer (one float4 granule of the [16][4H] tile per thread)
+  // H = 64, whose compute waves store dz and dx themselves. dz: one float4 granule of the [16][4H]
+  // tile per thread
   const int gz_seq = tid / (G4 / 4), gz_c = (tid % (G4 / 4)) * 4;
   __bf16* zbase = S.dz + (size_t)(row0 + gz_seq) * G4 + gz_c;
   const size_t zstep = (size_t)Mp * G4;
@@ -1548,14 +1712,9 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
   auto store_dx = [&](int buf, int ts, unsigned tag) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      float v;
-      if constexpr (SK) {
-        v = 0.f;
+      float v = 0.f;
 #pragma unroll
-        for (int g = 0; g < KXG; ++g) v += xpart[buf][g][xrow[q]][xk[q]];
-      } else {
-        v = dxs[buf][xrow[q]][xk[q]];
-      }
+      for (int g = 0; g < KXG; ++g) v += xpart[buf][g][xrow[q]][xk[q]];
       const size_t o = (size_t)xo[q] + (size_t)ts * xstep;
       if constexpr (XO) st_granule(S.sout + o, v, tag);
       else S.dx[o] = v;
@@ -1567,191 +1726,6 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
     tw = max(tw, 0);
     const int st = src_t(tw);
     if (st >= 0) (void)chain_wait(S.din + eoff + (size_t)st * hstep, tagb | (unsigned)st, ctl);
-  }
-  if constexpr (!SK) {
-    // ------------------------------------------------------------------ H = 16: the pipelined step
-    // The bottom layers' T reverse steps are the backward's critical path, so between two barriers only
-    // what needs dh_rec stays behind the MFMAs, and the hand-off staging runs while LDS reads fly:
-    //
-    //   barrier s                      dz(s) is in zs[s & 1], dh(s + 1) in dhs[(s + 1) & 1]
-    //   ds_read_b128 of dz(s) K-block 0, MFMA as soon as it is there
-    //   ds_read_b128 of K-block 1 and the read of dh(s + 1)
-    //     while they fly: dh(s + 2) from its ring slot (tag check, un-pool select) -> dhs[s & 1],
-    //                     ring load of dh(s + 2 + D)
-    //   second MFMA: dh_rec = U dz(s)
-    //     in its shadow: gates of step s + 1 unpacked, tanh(c), every factor that does not need dh_rec
-    //   dh = dh(s + 1) + dh_rec, dct, dc, four products, bf16, dz(s + 1) -> zs[(s + 1) & 1]
-    //   state load of step s + 1 + D into the slot just consumed
-    //
-    // dhs[s & 1] was last read after barrier s - 1 and is read again after barrier s + 1, so two
-    // buffers suffice. Steps past the sequence (s >= T, and the un-pooling tail past the last pooling
-    // window) carry no source granule: they are never waited for and stage a zero. The hoisted
-    // factors reassociate the cell's products (dct * (g * i * (1 - i)) for ((dct * g) * i) * (1 - i)):
-    // bf16 rounding flips in dz against the per-layer kernels, nothing else.
-    // Measured placements (profiles/chain_bwd_h16_pipeline_ab.txt): both K-block reads ahead of the
-    // first MFMA, tanh(c) ahead of the MFMAs, the state load pinned behind the dz stores or moved into
-    // the MFMA shadow, chain_wait inlined, a ring of 2 / 3 / 5 / 6 steps: all slower than this order.
-    // Wave-uniform cursors replace the per-step address products: the saved state and the dh source
-    // are walked one step at a time, and every load is a fixed base, a 32-bit step offset and a lane
-    // offset (the arrays of an H = 16 stage stay below 4 GiB: lstm_chain_bwd checks it).
-    static_assert(PUBW && D >= 2, "H = 16 stage: publisher waves, ring of at least two steps");
-    constexpr unsigned NOSRC = 0xFFFFFFFFu;
-    const unsigned lo8 = (unsigned)((tile * NW + w) * 64 + lane) * 8u;    // this lane's cell in a state step (bytes of g)
-    const unsigned gstr = (unsigned)(ntiles * NW * 64 * 8);               // bytes per step of g (c: half)
-    const char* gbase = reinterpret_cast<const char*>(S.g);
-    const char* cbase = reinterpret_cast<const char*>(S.c);
-    int stt = T - 1;                                                      // time of the next state load
-    auto state_load = [&](int J) {
-      const unsigned o = (unsigned)__builtin_amdgcn_readfirstlane(stt) * gstr + lo8;   // (a scalar product)
-      rg[J] = *reinterpret_cast<const uint2*>(gbase + o);
-      rc[J] = *reinterpret_cast<const float*>(cbase + (o >> 1));
-      stt = max(stt - 1, 0);                                              // (steps past the sequence reload t = 0)
-    };
-    // dh source cursor: time dtt (< 0 past the sequence), source row dst and phase dph = dtt - dst P of
-    // an un-pooling stage (dph >= P: the tail past the last pooling window, read from the last row)
-    constexpr unsigned ESZ = SRC ? 8 : 4;
-    const unsigned eo = (unsigned)eoff;
-    const unsigned hrow = (unsigned)hstep;
-    const char* dbase = SRC ? reinterpret_cast<const char*>(S.din) : reinterpret_cast<const char*>(S.dh);
-    const char* pbase = reinterpret_cast<const char*>(S.pidx);
-    int dtt = T - 1;
-    int dst = UP ? min(divp(dtt), Ts - 1) : dtt;
-    int dph = UP ? dtt - dst * P : 0;
-    const unsigned dlim = (unsigned)(UP ? Ts * P : T);                    // times with a source granule: [0, dlim)
-    unsigned rinf[D];                 // per ring slot: phase << 12 | source row, NOSRC: no source granule
-    auto ring_load = [&](int J) {
-      const unsigned o = (unsigned)max(dst, 0) * hrow + eo;
-      if constexpr (SRC) rq[J] = ld_granule(reinterpret_cast<const unsigned long long*>(dbase + o * ESZ));
-      else rq[J] = (unsigned long long)__float_as_uint(*reinterpret_cast<const float*>(dbase + o * ESZ));
-      if constexpr (UP) ri[J] = (unsigned)*reinterpret_cast<const unsigned char*>(pbase + o);
-      else ri[J] = 0u;
-      const unsigned inf = ((unsigned)dph << 12) | (unsigned)dst;
-      rinf[J] = (unsigned)dtt < dlim ? inf : NOSRC;
-      --dtt;
-      if constexpr (UP) {
-        const bool wrap = dph == 0;                                       // the source row changes
-        dst = wrap ? dst - 1 : dst;
-        dph = wrap ? P - 1 : dph - 1;
-      } else {
-        --dst;
-      }
-    };
-    auto stage = [&](int J) -> float {
-      const unsigned inf = rinf[J];
-      const bool has = inf != NOSRC;
-      if constexpr (SRC) {
-        const unsigned want = tagb | (inf & 0xfffu);
-        const bool bad = has && (unsigned)(rq[J] >> 32) != want;
-        if (__builtin_amdgcn_ballot_w64(bad) != 0) {
-          rq[J] = chain_wait(S.din + eoff + (size_t)(inf & 0xfffu) * hstep, want, ctl);
-        }
-      }
-      const float v = __uint_as_float((unsigned)rq[J]);
-      bool keep = has;
-      if constexpr (UP) keep = keep && ri[J] == (inf >> 12);
-      return keep ? v : 0.f;
-    };
-    // the cell of one step in two halves: what the saved state alone gives, and what needs dh_rec
-    // (tanh(c) stays a statement of its own: folded into cell_pre as a local the compiler scheduled the
-    // step differently, same-box 0.2383-0.2403 against 0.2350-0.2360 ms/step)
-    float tc, fo, ff, z0, z1, z2, z3;
-    auto cell_pre_c = [&](int J) { tc = tanhf_fast(rc[J]); };
-    auto cell_pre = [&](int J, int JN, int tt) {
-      const float cp = rc[JN] * (tt > 0 ? 1.f : 0.f);                     // c_{t-1}
-      const float4 g4 = gates_unpack(rg[J]);
-      fo = g4.w * (1.f - tc * tc);
-      ff = g4.y;
-      z0 = g4.z * g4.x * (1.f - g4.x);
-      z1 = cp * g4.y * (1.f - g4.y);
-      z2 = g4.x * (1.f - g4.z * g4.z);
-      z3 = tc * g4.w * (1.f - g4.w);
-    };
-    float dc = 0.f;
-    auto cell_tail = [&](int pb, float dh) {
-      const float dct = dc + dh * fo;
-      dc = dct * ff;
-      zs[pb][col][chz(col, 0 * H + unit)] = (__bf16)(dct * z0);
-      zs[pb][col][chz(col, 1 * H + unit)] = (__bf16)(dct * z1);
-      zs[pb][col][chz(col, 2 * H + unit)] = (__bf16)(dct * z2);
-      zs[pb][col][chz(col, 3 * H + unit)] = (__bf16)(dh * z3);
-    };
-
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-      state_load(j);
-      ring_load(j);
-    }
-    __syncthreads();
-    dhs[0][tid / H][tid % H] = stage(0);          // dh of steps 0 and 1
-    ring_load(0);
-    dhs[1][tid / H][tid % H] = stage(1);
-    ring_load(1);
-    __syncthreads();
-    float dhn = dhs[0][col][unit];
-    if (tid == 0 && S.trace_mid) S.trace_mid[blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
-    cell_pre_c(0);
-    cell_pre(0, 1, T - 1);                        // step 0: no dh_rec yet
-    cell_tail(0, dhn);
-    state_load(0);
-
-    long long* pr = (S.prof != nullptr && tile == 0) ? S.prof : nullptr;
-    for (int s0 = 0; s0 < T; s0 += D) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) {
-        const int s = s0 + j;
-        const int p = s & 1;
-        const int j1 = (j + 1) % D, j2 = (j + 2) % D;
-        lds_barrier();
-        chain_mark(pr, s, 0);
-        const bf16x8_t bz0 = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 8 * quad)]);
-        __builtin_amdgcn_sched_barrier(0);         // (the fences keep this order: see the stage's header)
-        f32x4_t a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[0], bz0, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        const bf16x8_t bz1 = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 + 8 * quad)]);
-        dhn = dhs[p ^ 1][col][unit];
-        dhs[p][tid / H][tid % H] = stage(j2);     // dh of step s + 2, then its slot's next load
-        ring_load(j2);
-        chain_mark(pr, s, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const f32x4_t a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[1], bz1, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        cell_pre_c(j1);
-        cell_pre(j1, j2, T - 2 - s);
-        __builtin_amdgcn_sched_barrier(0);
-        float dhr = a0[0] + a1[0];
-#ifdef GQ_CHAIN_PROF
-        if (pr != nullptr) asm volatile("" : "+v"(dhr));
-#endif
-        chain_mark(pr, s, 2);
-        cell_tail(p ^ 1, dhn + dhr);
-        chain_mark(pr, s, 3);
-        state_load(j1);
-        if constexpr (!DXW) {                      // dx^T = W dz^T of step s (DXW: the dx wave's)
-          if (s < T) {
-#pragma unroll
-            for (int q = 0; q < TX; ++q) {
-              const int xb = w + NW * q;
-              if (xb < NXB) {
-                f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < KB; ++k) {
-                  const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 * k + 8 * quad)]);
-                  bf16x8_t wa;
-                  if constexpr (L::WL) wa = *reinterpret_cast<const bf16x8_t*>(&wl[xb][col][32 * k + 8 * quad]);
-                  else wa = wfr[q][k];
-                  a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, bz, a, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dxs[p][col][16 * xb + 4 * quad + r] = a[r];
-              }
-            }
-          }
-        }
-        chain_mark(pr, s, 4);
-      }
-    }
-    __syncthreads();
-    return;
   }
 #pragma unroll
   for (int j = 0; j < D; ++j) load(j, j);
@@ -1779,10 +1753,10 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
         const float tc = tanhf_fast(rc[j]);
         const float dct = dc + dh * g4.w * (1.f - tc * tc);
         dc = dct * g4.y;
-        zs[p][col][chz(col, 0 * H + unit)] = (__bf16)(dct * g4.z * g4.x * (1.f - g4.x));
-        zs[p][col][chz(col, 1 * H + unit)] = (__bf16)(dct * cp * g4.y * (1.f - g4.y));
-        zs[p][col][chz(col, 2 * H + unit)] = (__bf16)(dct * g4.x * (1.f - g4.z * g4.z));
-        zs[p][col][chz(col, 3 * H + unit)] = (__bf16)(dh * tc * g4.w * (1.f - g4.w));
+        zs[p][col][0 * H + unit] = (__bf16)(dct * g4.z * g4.x * (1.f - g4.x));
+        zs[p][col][1 * H + unit] = (__bf16)(dct * cp * g4.y * (1.f - g4.y));
+        zs[p][col][2 * H + unit] = (__bf16)(dct * g4.x * (1.f - g4.z * g4.z));
+        zs[p][col][3 * H + unit] = (__bf16)(dh * tc * g4.w * (1.f - g4.w));
       }
       {   // state of step s + D and the dh of step s + 1 (time t - 1)
         const int tt = max(T - 1 - (s + D), 0);
@@ -1804,17 +1778,17 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
       lds_barrier();
       chain_mark(pr, s, 3);
       dhn = dhs[p ^ 1][col][unit];
-      if constexpr (SK) {   // partial products of this wave's K slices -> LDS
+      {   // partial products of this wave's K slices -> LDS
         f32x4_t a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < KPG; ++q) {
-          const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 * (kg * KPG + q) + 8 * quad)]);
+          const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][32 * (kg * KPG + q) + 8 * quad]);
           a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[q], bz, a, 0, 0, 0);
         }
         f32x4_t b = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < KPX; ++q) {
-          const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][chz(col, 32 * (kx * KPX + q) + 8 * quad)]);
+          const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][32 * (kx * KPX + q) + 8 * quad]);
           b = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufk[q], bz, b, 0, 0, 0);
         }
 #pragma unroll
@@ -1824,16 +1798,16 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
         }
       }
       chain_mark(pr, s, 4);
-      if constexpr (!PUBW) {   // dz tile -> HBM (weight-gradient pass; else the publisher stores it)
-        const uint2 zv = *reinterpret_cast<const uint2*>(&zs[p][gz_seq][chz(gz_seq, gz_c)]);
+      if constexpr (!PUBW) {   // dz tile -> HBM (weight-gradient pass; else the dz wave stores it)
+        const uint2 zv = *reinterpret_cast<const uint2*>(&zs[p][gz_seq][gz_c]);
         const int tz = t >= 0 ? t : T;
         *reinterpret_cast<uint2*>(zbase + (size_t)tz * zstep) = zv;
       }
-      {   // previous step's dx tile (time t + 1) -> stream / HBM; steps outside write row T
+      if constexpr (!PUBW) {   // previous step's dx tile (time t + 1) -> stream / HBM; steps outside write row T
         const int ts = (s >= 1 && s <= T) ? t + 1 : T;
-        if constexpr (!PUBW) store_dx(p ^ 1, ts, tagb | (unsigned)ts);
+        store_dx(p ^ 1, ts, tagb | (unsigned)ts);
       }
-      if constexpr (SK) {   // the partial tiles meet: dh_{t-1} of this lane's cell
+      {   // the partial tiles meet: dh_{t-1} of this lane's cell
         lds_barrier();
         float sdh = 0.f;
 #pragma unroll
@@ -1845,322 +1819,6 @@ __device__ __forceinline__ void chain_bwd_stage(const ChainBStage S, int tile, i
   }
   __syncthreads();
   if constexpr (!PUBW) store_dx((T - 1) & 1, 0, tagb);     // dx tile of t = 0
-}
-
-// The H = 16 reverse recurrence (the bottom layers' 181 steps: the backward's critical path) with the
-// forward's role split. Compute waves: per step, the cell's gate gradients from LDS inputs only (the
-// packed gates, c_t and c_{t-1} as one 16-byte record, dh from the stage above), dz to LDS, one
-// barrier, dh_rec = U dz and dx = W dz by MFMA from LDS; no global memory access at all. D rotating
-// I/O waves: wave k stages the records and the (tag-checked, un-pooled) dh tile of every step
-// s = k (mod D), loaded D steps ahead, with 16-byte loads of the tile's contiguous cell block. A
-// publisher wave stores each step's dz tile (16-byte stores) and publishes its dx, one step later.
-template <int H>
-struct ChainBIoLds {
-  static constexpr int ZS = 2 * 16 * (4 * H + 8) * 2;
-  static constexpr int DH = 2 * 16 * TMC<H>::HP * 4;
-  static constexpr int DX = 2 * 16 * 32 * 2 * 4;          // dx tiles (KX <= 2)
-  static constexpr int RC = 2 * TMC<H>::NT * 16;          // {gates, c_t, c_{t-1}} records
-  static constexpr int BYTES = ZS + DH + DX + RC;
-};
-__host__ __device__ constexpr int chainb_io_threads(int nt, int d) { return nt + 64 * d * CHAINB_G + 64; }
-template <int V>
-struct ChIc { static constexpr int value = V; };
-
-template <int H, int KX, int D, bool SRC, bool UP, bool XO>
-__device__ __forceinline__ void chain_bwd_stage_io(const ChainBStage S, int tile, int ntiles, int Mp, unsigned tagb,
-                                                   int* ctl, char* smem) {
-  using C = TMC<H>;
-  constexpr int NW = C::NW, NT = C::NT, G4 = C::G4, KB = C::KB;
-  constexpr int NXB = KX * 2;
-  constexpr int TX = (NXB + NW - 1) / NW;
-  static_assert(C::CPL == 1 && 16 * H == NT && NT % 256 == 0, "one dh element per compute lane");
-  constexpr int CPLN = NT / 64;                     // cells per I/O lane (whole tile per I/O wave)
-  static_assert(CPLN % 4 == 0 || CPLN == 4, "I/O lanes move cells four at a time");
-  using L = ChainBIoLds<H>;
-  static_assert(L::BYTES <= CHAINB_LDS_STAGE, "chain bwd I/O LDS layout");
-  auto zs = reinterpret_cast<__bf16 (*)[16][G4 + 8]>(smem);
-  auto dhs = reinterpret_cast<float (*)[16][C::HP]>(smem + L::ZS);
-  auto dxs = reinterpret_cast<float (*)[16][32 * KX]>(smem + L::ZS + L::DH);
-  auto rec = reinterpret_cast<uint4 (*)[NT]>(smem + L::ZS + L::DH + L::DX);
-
-  const int T = S.T, Din = S.Din, Dw = S.Dw, P = S.P, Ts = S.Ts;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int col = lane & 15, quad = lane >> 4;
-  const int row0 = tile * 16;
-  constexpr int G = CHAINB_G;
-  static_assert(G == 1 || G == 2, "backward I/O group: one wave, or a record wave and a dh wave");
-  const bool compute = w < NW;
-  const bool publisher = w == NW + D * G;
-  const int iow = (w - NW) / G;                     // I/O group: steps s = iow (mod D)
-  const int sub = (w - NW) % G;                     // (G = 2: 0 loads the cell records, 1 the dh tile)
-  constexpr int NTL = chainb_io_threads(NT, D);
-  for (int i = tid; i < 2 * 16 * C::HP; i += NTL) (&dhs[0][0][0])[i] = 0.f;
-  const size_t hstep = (size_t)Mp * H;
-  const size_t zstep = (size_t)Mp * G4;
-  const size_t xstep = (size_t)Mp * Din;
-  // source time of the dh of time tt (-1: past the last pooling window -> zero gradient)
-  auto src_t = [&](int tt) {
-    if constexpr (UP) return tt < Ts * P ? tt / P : -1;
-    else return tt;
-  };
-  long long* pr = (S.prof != nullptr && tile == 0) ? S.prof : nullptr;
-
-  // ---------------------------------------------------------------- I/O waves
-  // one slot: this tile's 4 cells x {gates (2 x 16 B), c_t, c_{t-1}} and 2 dh pairs (+ argmax bytes)
-  constexpr int NDP = NT / 2 / 64;                  // dh pairs per lane
-  uint4 sg[CPLN / 2];
-  float4 sc[CPLN / 4], scp[CPLN / 4];
-  u64x2_t sq[NDP];
-  unsigned short si[NDP];
-  // (SB: 0 = records only, 1 = dh only, 2 = both; a compile-time choice so no branch sits between a
-  // wave's loads and their use)
-  auto io_load = [&](auto sbc, int ss) {            // the inputs of reverse step ss
-    constexpr int SB = decltype(sbc)::value;
-    const int tt = max(T - 1 - ss, 0);
-    const size_t cell0 = ((size_t)tt * ntiles + tile) * NT;
-    const size_t cellp = ((size_t)max(tt - 1, 0) * ntiles + tile) * NT;
-    // (lane's cells: groups of four, 4 (lane + 64 q) + i; gates of a group = two 16-byte halves)
-    if constexpr (SB != 1) {
-#pragma unroll
-      for (int q = 0; q < CPLN / 2; ++q)
-        sg[q] = *reinterpret_cast<const uint4*>(S.g + (cell0 + 4 * (lane + 64 * (q / 2)) + 2 * (q % 2)) * 4);
-#pragma unroll
-      for (int q = 0; q < CPLN / 4; ++q) {
-        sc[q] = *reinterpret_cast<const float4*>(S.c + cell0 + 4 * (lane + 64 * q));
-        scp[q] = *reinterpret_cast<const float4*>(S.c + cellp + 4 * (lane + 64 * q));
-      }
-    }
-    const int st = max(src_t(tt), 0);
-#pragma unroll
-    for (int q = 0; q < (SB != 0 ? NDP : 0); ++q) {
-      const size_t e = (size_t)row0 * H + 2 * (lane + 64 * q) + (size_t)st * hstep;
-      if constexpr (SRC) sq[q] = u64x2_t{ld_granule(S.din + e), ld_granule(S.din + e + 1)};
-      else {
-        const float2 v = *reinterpret_cast<const float2*>(S.dh + e);
-        sq[q] = u64x2_t{(unsigned long long)__float_as_uint(v.x), (unsigned long long)__float_as_uint(v.y)};
-      }
-      if constexpr (UP) si[q] = *reinterpret_cast<const unsigned short*>(S.pidx + e);
-      else si[q] = 0;
-    }
-  };
-  auto io_stage = [&](auto sbc, int buf, int ss) {  // step ss's records and dh tile -> LDS buffer buf
-    constexpr int SB = decltype(sbc)::value;
-    const int tt = T - 1 - ss;
-    const int st = src_t(tt);
-    if constexpr (SRC && SB != 0) {
-      bool bad = false;
-#pragma unroll
-      for (int q = 0; q < NDP; ++q)
-        bad |= st >= 0 && ((unsigned)(sq[q].x >> 32) != (tagb | (unsigned)st) || (unsigned)(sq[q].y >> 32) != (tagb | (unsigned)st));
-      if (__builtin_amdgcn_ballot_w64(bad) != 0) {   // re-poll the whole tile at once (bounded)
-        const int lim0 = __hip_atomic_load(ctl + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int lim = lim0 > 0 ? lim0 : CHAIN_SPIN;
-        int nap = 1;
-        for (int it = 0;; ++it) {
-#pragma unroll
-          for (int q = 0; q < NDP; ++q) {
-            const size_t e = (size_t)row0 * H + 2 * (lane + 64 * q) + (size_t)max(st, 0) * hstep;
-            sq[q] = u64x2_t{ld_granule(S.din + e), ld_granule(S.din + e + 1)};
-          }
-          bad = false;
-#pragma unroll
-          for (int q = 0; q < NDP; ++q)
-            bad |= (unsigned)(sq[q].x >> 32) != (tagb | (unsigned)st) || (unsigned)(sq[q].y >> 32) != (tagb | (unsigned)st);
-          if (__builtin_amdgcn_ballot_w64(bad) == 0) break;
-          if (it >= lim) {
-            __hip_atomic_store(ctl + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-          for (int k = 0; k < nap; ++k) __builtin_amdgcn_s_sleep(2);
-          nap = min(nap * 2, CHAIN_RP_NAPMAX);
-        }
-      }
-    }
-    const unsigned ph = UP ? (unsigned)(tt % P) : 0u;
-#pragma unroll
-    for (int q = 0; q < (SB != 0 ? NDP : 0); ++q) {
-      const int e = 2 * (lane + 64 * q);
-      const float v0 = __uint_as_float((unsigned)sq[q].x), v1 = __uint_as_float((unsigned)sq[q].y);
-      const bool k0 = st >= 0 && (!UP || (si[q] & 0xffu) == ph), k1 = st >= 0 && (!UP || (si[q] >> 8) == ph);
-      *reinterpret_cast<float2*>(&dhs[buf][e / H][e % H]) = make_float2(k0 ? v0 : 0.f, k1 ? v1 : 0.f);
-    }
-    const float cm = tt > 0 ? 1.f : 0.f;
-#pragma unroll
-    for (int q = 0; q < (SB != 1 ? CPLN / 4 : 0); ++q) {
-      const int c0 = 4 * (lane + 64 * q);
-      const uint4 ga = sg[2 * q], gb = sg[2 * q + 1];
-      rec[buf][c0 + 0] = make_uint4(ga.x, ga.y, __float_as_uint(sc[q].x), __float_as_uint(scp[q].x * cm));
-      rec[buf][c0 + 1] = make_uint4(ga.z, ga.w, __float_as_uint(sc[q].y), __float_as_uint(scp[q].y * cm));
-      rec[buf][c0 + 2] = make_uint4(gb.x, gb.y, __float_as_uint(sc[q].z), __float_as_uint(scp[q].z * cm));
-      rec[buf][c0 + 3] = make_uint4(gb.z, gb.w, __float_as_uint(sc[q].w), __float_as_uint(scp[q].w * cm));
-    }
-  };
-
-  // ---------------------------------------------------------------- compute state
-  const int unit = 4 * w + quad;
-  const int au = 4 * w + (col >> 2);
-  bf16x8_t ufr[KB];
-  bf16x8_t wfr[TX][KB];
-  if (compute) {
-#pragma unroll
-    for (int k = 0; k < KB; ++k) {
-      bf16x8_t v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float val = S.U[(size_t)au * G4 + 32 * k + 8 * quad + j];
-        v[j] = (__bf16)(val * ((col & 3) == 0 ? 1.f : 0.f));
-      }
-      ufr[k] = v;
-    }
-#pragma unroll
-    for (int q = 0; q < TX; ++q) {
-      const int xb = w + NW * q;
-      const int din = 16 * xb + col;
-#pragma unroll
-      for (int k = 0; k < KB; ++k) {
-        bf16x8_t v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          v[j] = (__bf16)(S.W[(size_t)min(din, Dw - 1) * G4 + 32 * k + 8 * quad + j] *
-                          ((xb < NXB && din < Dw) ? 1.f : 0.f));
-        wfr[q][k] = v;
-      }
-    }
-  }
-
-  // ---------------------------------------------------------------- prologue
-  // run f with this I/O wave's share as a compile-time constant
-  auto io_dispatch = [&](auto f) {
-    if constexpr (G == 1) f(ChIc<2>{});
-    else if (sub == 0) f(ChIc<0>{});
-    else f(ChIc<1>{});
-  };
-  if (!compute && !publisher) {
-    if constexpr (SRC) {    // start once the stage above is D + LEAD steps ahead (see the forward)
-      const int tw = max(T - 1 - (D + CHAINB_LEAD), 0);
-      const int st = src_t(tw);
-      if (st >= 0) (void)chain_wait(S.din + (size_t)row0 * H + (size_t)st * hstep, tagb | (unsigned)st, ctl);
-    }
-    io_dispatch([&](auto sbc) { io_load(sbc, min(iow, T - 1)); });
-  }
-  __syncthreads();
-  if (!compute && !publisher && iow == 0) {
-    io_dispatch([&](auto sbc) {
-      io_stage(sbc, 0, 0);
-      if (!CHAIN_DEFER_LD) io_load(sbc, min(D, T - 1));
-    });
-  }
-  __syncthreads();
-  if (tid == 0 && S.trace_mid) S.trace_mid[blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
-
-  if (compute) {
-    if (CHAIN_PRIO > 0) __builtin_amdgcn_s_setprio(CHAIN_PRIO);
-    float dc = 0.f, dhr = 0.f;
-    for (int s = 0; s < T; ++s) {
-      const int t = T - 1 - s;
-      const int p = s & 1;
-      chain_mark(pr, s, 0);
-      {   // cell: gate gradients of (unit, sequence col) at time t
-        const uint4 r4 = rec[p][w * 64 + lane];
-        const float dh = dhs[p][col][unit] + dhr;
-        const float4 g4 = gates_unpack(make_uint2(r4.x, r4.y));
-        const float ct = __uint_as_float(r4.z), cp = __uint_as_float(r4.w);
-        const float tc = tanhf_fast(ct);
-        const float dct = dc + dh * g4.w * (1.f - tc * tc);
-        dc = dct * g4.y;
-        zs[p][col][0 * H + unit] = (__bf16)(dct * g4.z * g4.x * (1.f - g4.x));
-        zs[p][col][1 * H + unit] = (__bf16)(dct * cp * g4.y * (1.f - g4.y));
-        zs[p][col][2 * H + unit] = (__bf16)(dct * g4.x * (1.f - g4.z * g4.z));
-        zs[p][col][3 * H + unit] = (__bf16)(dh * tc * g4.w * (1.f - g4.w));
-      }
-      chain_mark(pr, s, 1);
-      lds_barrier();
-      chain_mark(pr, s, 2);
-      {   // dh_{t-1} = U dz_t (the serial chain), then dx^T = W dz^T
-        f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][32 * k + 8 * quad]);
-          if (k & 1) a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[k], bz, a1, 0, 0, 0);
-          else a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[k], bz, a0, 0, 0, 0);
-        }
-        dhr = a0[0] + a1[0];     // (U^T rows with (col & 3) == 0: element 0 is this lane's unit)
-      }
-      chain_mark(pr, s, 3);
-#pragma unroll
-      for (int q = 0; q < TX; ++q) {
-        const int xb = w + NW * q;
-        if (xb < NXB) {
-          f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int k = 0; k < KB; ++k) {
-            const bf16x8_t bz = *reinterpret_cast<const bf16x8_t*>(&zs[p][col][32 * k + 8 * quad]);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfr[q][k], bz, a, 0, 0, 0);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dxs[p][col][16 * xb + 4 * quad + r] = a[r];
-        }
-      }
-      chain_mark(pr, s, 4);
-    }
-    __builtin_amdgcn_s_setprio(0);
-  } else if (publisher) {
-    // after barrier s: step s's dz tile is complete (compute only reads it until barrier s + 1) and
-    // step s - 1's dx tile too (written after barrier s - 1)
-    auto store_dz = [&](int ss) {
-      const int tz = T - 1 - ss;
-      const int pb = ss & 1;
-      __bf16* zt = S.dz + ((size_t)tz * Mp + row0) * G4;
-#pragma unroll
-      for (int q = lane; q < 16 * G4 / 8; q += 64) {
-        const int e = 8 * q;
-        *reinterpret_cast<uint4*>(zt + e) = *reinterpret_cast<const uint4*>(&zs[pb][e / G4][e % G4]);
-      }
-    };
-    auto publish = [&](int ss) {            // step ss's dx tile
-      const int tz = T - 1 - ss;
-      const int pb = ss & 1;
-      const unsigned tag = tagb | (unsigned)tz;
-      const size_t xo = ((size_t)tz * Mp + row0) * Din;
-      for (int e = lane; e < 16 * Din; e += 64) {
-        const float v = dxs[pb][e / Din][e % Din];
-        if constexpr (XO) st_granule(S.sout + xo + e, v, tag);
-        else S.dx[xo + e] = v;
-      }
-    };
-    for (int s = 0; s < T; ++s) {
-      lds_barrier();
-      store_dz(s);
-      if (s >= 1) publish(s - 1);
-    }
-    __syncthreads();
-    publish(T - 1);
-    return;
-  } else {
-    io_dispatch([&](auto sbc) {
-      const bool mk = lane == 0 && sub == G - 1;      // (phase marks: the dh wave, which tag-checks)
-      int kt = (iow + D - 1) % D;           // steps until this group's turn
-      int next_ld = iow == 0 ? D : -1;      // (deferred loads: see the forward's I/O loop)
-      for (int s = 0; s < T; ++s) {
-        if (CHAIN_DEFER_LD && next_ld >= 0) {
-          io_load(sbc, min(next_ld, T - 1));
-          next_ld = -1;
-        }
-        if (kt == 0 && s + 1 < T) {
-          if (mk) chain_mark_wave(pr, s, 5);
-          io_stage(sbc, (s + 1) & 1, s + 1);
-          if (mk) chain_mark_wave(pr, s, 6);
-          if (CHAIN_DEFER_LD) next_ld = s + 1 + D;
-          else io_load(sbc, min(s + 1 + D, T - 1));
-          if (mk) chain_mark_wave(pr, s, 7);
-        }
-        kt = kt == 0 ? D - 1 : kt - 1;
-        lds_barrier();
-      }
-    });
-  }
-  __syncthreads();
 }
 
 // time4's backward on one 16-sequence tile with 1024 threads: the head backward (chain_head.h,
@@ -2324,15 +1982,15 @@ __global__ __launch_bounds__(1024) void lstm_chain_bwd_kernel(ChainBArgs A) {
   const ChainBStage S = A.st[s];
   const int H = S.H, KX = S.KX;
   const bool src = s > 0 || A.t4.on;              // (stage 0 then reads time4's dx granules)
+  // (the stage function of a hidden size, called straight from the kernel: a wrapper template that
+  // picked it changed the generated code)
+#define GQ_CHAINB_STAGE_16(KXX, DD, SRCV, UPV, XOV) chain_bwd_stage16<KXX, DD, SRCV, UPV, XOV>
+#define GQ_CHAINB_STAGE_32(KXX, DD, SRCV, UPV, XOV) chain_bwd_stage_sk<32, KXX, DD, SRCV, UPV, XOV>
+#define GQ_CHAINB_STAGE_64(KXX, DD, SRCV, UPV, XOV) chain_bwd_stage_sk<64, KXX, DD, SRCV, UPV, XOV>
 #define GQ_CHAINB_BODY3(HH, KXX, DD, SRCV, UPV, XOV)                                    \
   {                                                                                     \
-    if constexpr (HH == 16 && CHAINB_IO) {                                              \
-      if (threadIdx.x >= chainb_io_threads(TMC<HH>::NT, DD)) return;                    \
-      chain_bwd_stage_io<HH, KXX, DD, SRCV, UPV, XOV>(S, tile, A.ntiles, A.Mp, tagb, A.ctl, smem); \
-    } else {                                                                            \
-      if (threadIdx.x >= chainb_live_threads(HH, TMC<HH>::NT)) return;                   \
-      chain_bwd_stage<HH, KXX, DD, SRCV, UPV, XOV>(S, tile, A.ntiles, A.Mp, tagb, A.ctl, smem); \
-    }                                                                                   \
+    if (threadIdx.x >= chainb_live_threads(HH, TMC<HH>::NT)) return;                    \
+    GQ_CHAINB_STAGE_##HH(KXX, DD, SRCV, UPV, XOV)(S, tile, A.ntiles, A.Mp, tagb, A.ctl, smem); \
   }
 #define GQ_CHAINB_BODY2(HH, KXX, DD, SRCV, UPV)                                         \
   if (!SRCV || S.sout) GQ_CHAINB_BODY3(HH, KXX, DD, SRCV, UPV, true)                    \
@@ -2344,16 +2002,15 @@ __global__ __launch_bounds__(1024) void lstm_chain_bwd_kernel(ChainBArgs A) {
     else { if (S.P > 0) { GQ_CHAINB_BODY3(HH, KXX, DD, false, true, true) }             \
            else { GQ_CHAINB_BODY3(HH, KXX, DD, false, false, true) } }                  \
   }
-#ifdef CHAINB_ONLY
-  { GQ_CHAINB_BODY3(CHAINB_ONLY, CHAINB_KX, CHAINB_DONLY, CHAINB_SRC, CHAINB_UP, true) }
-#else
   if (H == 16) { if (KX == 1) GQ_CHAINB_BODY(16, 1, CHAINB_D16) else GQ_CHAINB_BODY(16, 2, CHAINB_D16) }
   else if (H == 32) { if (KX == 1) GQ_CHAINB_BODY(32, 1, CHAINB_D32) else GQ_CHAINB_BODY(32, 2, CHAINB_D32) }
   else { if (KX == 1) GQ_CHAINB_BODY(64, 1, CHAINB_D64) else GQ_CHAINB_BODY(64, 2, CHAINB_D64) }
-#endif
 #undef GQ_CHAINB_BODY
 #undef GQ_CHAINB_BODY2
 #undef GQ_CHAINB_BODY3
+#undef GQ_CHAINB_STAGE_16
+#undef GQ_CHAINB_STAGE_32
+#undef GQ_CHAINB_STAGE_64
   __syncthreads();
   if (threadIdx.x == 0) A.trace[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();
   chain_finish(A.ctl, nblk);
@@ -2854,36 +2511,8 @@ static std::vector<at::Tensor> chain_bwd_setup(ChainBArgs& A, std::vector<at::Te
     S.dz = bf16_ptr(dz);
     dzs.push_back(dz);
     const bool last = s + 1 == ns && ns > 1;     // (a single stage publishes: profiling)
-    // producer-side un-pooling of the stage below's input pool (ChainBStage::uidx)
-    S.uidx = nullptr;
-    S.uP = 0;
-    S.uT = 0;
-    S.punp = s > 0 ? A.st[s - 1].uidx != nullptr : 0;
-    int sT = T;                                  // rows of this stage's dx stream
-    if (!last && s + 1 < ns && pool[s + 1] > 0) {
-      static const bool on = [] {
-        const char* e = std::getenv("GNNQC_CHAINB_PUNPOOL");
-        return CHAINB_PUNPOOL && (e == nullptr || std::atoi(e) != 0);
-      }();
-      const int Hs = H, KXs = (Din + 31) / 32;
-      const int stage_bytes = Hs >= 32 ? (KXs == 1 ? (Hs == 32 ? ChainBLdsSK<32, 1>::BYTES : ChainBLdsSK<64, 1>::BYTES)
-                                                   : (Hs == 32 ? ChainBLdsSK<32, 2>::BYTES : ChainBLdsSK<64, 2>::BYTES))
-                                       : (KXs == 1 ? ChainBLds<16, 1>::BYTES : ChainBLds<16, 2>::BYTES);
-      const long ub = (long)T * 16 * Din;
-      const int uT = (int)T_in[s + 1];
-      // (the publisher wave un-pools: H = 64 stages fill the workgroup with compute waves and store dx themselves)
-      if (on && 16 * H + 64 <= 1024 && (stage_bytes + 15) / 16 * 16 + ub <= CHAINB_LDS && (long)uT * Mp * Din * 8 < (1L << 31) &&
-          T * (int)pool[s + 1] <= uT) {
-        TORCH_CHECK(pidx[s + 1].numel() == (long)T * Mp * Din && pidx[s + 1].scalar_type() == at::kByte,
-                    "lstm_chain_bwd: argmax bytes of stage ", s + 1);
-        S.uidx = pidx[s + 1].data_ptr<uint8_t>();
-        S.uP = (int)pool[s + 1];
-        S.uT = uT;
-        sT = uT;
-      }
-    }
     if (!last) {
-      at::Tensor so = at::empty({sT + 1, Mp, Din}, opt.dtype(at::kLong));
+      at::Tensor so = at::empty({T + 1, Mp, Din}, opt.dtype(at::kLong));
       S.sout = reinterpret_cast<unsigned long long*>(so.data_ptr<int64_t>());
       S.dx = nullptr;
       keep.push_back(so);

@@ -23,17 +23,18 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 
-def _layer(cuda_device, pool_size=3, seed=0):
+def _layer(cuda_device, pool_size=3, seed=0, din=18):
     from gnnqc.models.timelayer import TimeLayer
     torch.manual_seed(seed)
-    return TimeLayer(18, 16, 2, "lstm", pool_size=pool_size).to(cuda_device)
+    return TimeLayer(din, 16, 2, "lstm", pool_size=pool_size).to(cuda_device)
 
 
 def _padded(x):
-    """[M, T, 18] -> the time-major kernel input [T, Mp, 20] (zero rows / channels)."""
-    M = x.shape[0]
+    """[M, T, C] -> the time-major kernel input [T, Mp, C rounded up to 4] (zero rows / channels;
+    18 -> 20, 40 -> 40)."""
+    M, C = x.shape[0], x.shape[2]
     Mp = (M + 15) // 16 * 16
-    return F.pad(x.transpose(0, 1), (0, 2, 0, Mp - M)).contiguous()
+    return F.pad(x.transpose(0, 1), (0, -C % 4, 0, Mp - M)).contiguous()
 
 
 def _run(tl, h, M, monkeypatch, chain):
@@ -46,15 +47,17 @@ def _run(tl, h, M, monkeypatch, chain):
     return out.detach(), [hi.grad.clone()] + [p.grad.clone() for p in tl.parameters()]
 
 
-def _check_chain_vs_per_layer(cuda_device, monkeypatch, tl, T, M, nstages):
+def _check_chain_vs_per_layer(cuda_device, monkeypatch, tl, T, M, nstages, din=18):
     from gnnqc.utils.native import hip_ops
     monkeypatch.setenv("GNNQC_NO_PAIR", "1")
     monkeypatch.setenv("GNNQC_CHAIN_BWD", "1")
     gen = torch.Generator().manual_seed(1000 * T + M)
-    x = torch.randn(M, T, 18, generator=gen).to(cuda_device)
+    x = torch.randn(M, T, din, generator=gen).to(cuda_device)
     h = _padded(x)
     plan = tl._chain_plan(tl._sequence(), h)
     assert plan is not None and len(plan[0]) == nstages, plan
+    # stage 0 takes the whole padded input: more than 32 channels make it a KX = 2 stage
+    assert plan[0][0].units == 16 and plan[0][0].kernel.shape[0] == din and (h.shape[2] > 32) == (din > 32)
     o0, g0 = _run(tl, h, M, monkeypatch, False)
     st0 = hip_ops().lstm_chain_status(h).cpu()
     runs = [_run(tl, h, M, monkeypatch, True) for _ in range(3)]
@@ -90,6 +93,13 @@ def test_chain_bwd_identity_unpool_matches_per_layer(cuda_device, monkeypatch):
     """pool_size = 1: a two-stage chain whose un-pooling stage takes the identity (every step has a
     source step, phase 0), at a length that is no multiple of the ring depth."""
     _check_chain_vs_per_layer(cuda_device, monkeypatch, _layer(cuda_device, pool_size=1), 10, 40, 2)
+
+
+def test_chain_bwd_wide_input_first_stage_matches_per_layer(cuda_device, monkeypatch):
+    """A 40-channel input: stage 0 is an H = 16 stage with KX = 2 (33-64 input channels), the
+    instantiations that the 18-channel CML stack never reaches (forward stage 0 streaming fp32 x,
+    backward bottom stage with a two-block dx). Same bounds as the cases above."""
+    _check_chain_vs_per_layer(cuda_device, monkeypatch, _layer(cuda_device, din=40), 28, 16, 6, din=40)
 
 
 def test_chain_bwd_matches_fp64_oracle(cuda_device, monkeypatch):
