@@ -130,6 +130,12 @@ TORCH_LIBRARY(gnnqc, m) {
         "Tensor alpha, Tensor alphas, int Cp) -> Tensor");
   m.def("ig_gcn_pool_bwd(Tensor x, Tensor w, Tensor mask, Tensor g, Tensor W, Tensor b, Tensor scale, Tensor shift, "
         "Tensor alpha, Tensor alphas, Tensor wts, Tensor(a!) acc_x, Tensor(b!) acc_a, bool overwrite=False) -> ()");
+  m.def("ig_interp_base(Tensor v, Tensor b, Tensor alpha) -> Tensor");
+  m.def("ig_gcn_pool_fwd_base(Tensor x, Tensor xb, Tensor w, Tensor anom, Tensor ab, Tensor W, Tensor b, Tensor scale, "
+        "Tensor shift, Tensor alpha, Tensor alphas, int Cp) -> Tensor");
+  m.def("ig_gcn_pool_bwd_base(Tensor x, Tensor xb, Tensor w, Tensor mask, Tensor g, Tensor W, Tensor b, Tensor scale, "
+        "Tensor shift, Tensor alpha, Tensor alphas, Tensor wts, Tensor(a!) acc_x, Tensor(b!) acc_a, "
+        "bool overwrite=False) -> ()");
   m.def("ig_accum(Tensor(a!) acc, Tensor g, Tensor w) -> ()");
   m.def("ig_finalize(Tensor acc, Tensor v, int mode) -> Tensor");
   m.def("chain_poison(Tensor(a!) g, Tensor ext) -> ()");

@@ -13,7 +13,8 @@ def add_common(ap: argparse.ArgumentParser, ds_default: str = "cml"):
     ap.add_argument("--preproc", default=None, help="preprocessing YAML (default: packaged)")
     ap.add_argument("--model-config", default=None, help="model YAML (default: packaged)")
     ap.add_argument("--set", dest="overrides", action="append", default=[],
-                    help="override: pre.<key>=v for preprocessing, model.<key>=v for the model config")
+                    help="override: pre.<key>=v for preprocessing, model.<key>=v for the model config "
+                         "(explain: xai.<key>=v or integrated_gradients.<key>=v for the XAI config)")
     ap.add_argument("--synthetic", action="store_true", help="generate synthetic raw data instead of reading it")
     ap.add_argument("--sensors", type=int, default=None, help="synthetic: number of sensors (CML links / soil boxes)")
     ap.add_argument("--days", type=float, default=None, help="synthetic: length in days")

@@ -82,16 +82,36 @@ class IntegratedGradients:
     * ``path_pred`` [m+1, B] outputs along the path (gradient-saturation plots).
 
     SoilNet models emit one score per node; ``target`` [B] picks the node whose score
-    is explained (default: the highest-scoring valid node).
+    is explained (default: the highest-scoring valid node, chosen at x whatever the baseline).
+
+    ``baseline`` names the point the paths start from (the reference stubs ``mean`` and
+    ``random`` as "not implemented yet", ``:901-917``):
+
+    * ``"zero"``: x_a = a x (the reference's baseline);
+    * ``"mean"``: per (window, node, channel) the mean over the window's T steps, held constant
+      over time (the flagged series likewise; masked nodes stay zero) - "which deviation from
+      this window's own level drove the score";
+    * ``"random"``: ``n_baselines`` draws, each uniform between the window's per-(node, channel)
+      min and max over time, from a generator seeded with ``seed``; attributions and
+      ``path_pred`` are averaged over the draws;
+    * an explicit pair: ``attribute(batch, baselines=(xb, ab))``.
     """
+
+    BASELINES = ("zero", "mean", "random")
 
     def __init__(self, model, ds_type: str, m_steps: int = 100, baseline: str = "zero",
                  max_rows: int = 16384, scale_gradients: bool = True, negative_values: str = "keep",
-                 use_graph: bool = True):
-        if baseline != "zero":
-            raise NotImplementedError("only the zero baseline is implemented (as in the reference, :901-917)")
+                 use_graph: bool = True, n_baselines: int = 8, seed: int = 0):
+        if baseline not in self.BASELINES:
+            raise NotImplementedError(f"baseline must be one of {self.BASELINES} (or an explicit pair given to "
+                                      f"attribute(batch, baselines=...)), got {baseline!r}")
         if negative_values not in ("keep", "clip", "abs"):
             raise ValueError(f"negative_values must be keep/clip/abs, got {negative_values!r}")
+        if int(n_baselines) < 1:
+            raise ValueError(f"n_baselines must be at least 1, got {n_baselines!r}")
+        self.baseline = baseline
+        self.n_baselines = int(n_baselines)
+        self.seed = int(seed)
         self.model = model
         self.ds_type = ds_type
         self.m_steps = int(m_steps)
@@ -125,26 +145,109 @@ class IntegratedGradients:
         t = target.repeat(k)
         return out.gather(1, t[:, None])[:, 0]
 
-    def attribute(self, batch, target: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def attribute(self, batch, target: Optional[torch.Tensor] = None, baselines=None) -> Dict[str, torch.Tensor]:
+        """Attributions of ``batch`` relative to the engine's baseline kind, or to an explicit
+        baseline: ``baselines = (xb, ab)`` with the shapes of ``batch.x`` / ``batch.anom`` (``None``
+        for a tensor the model does not interpolate; a single tensor where there is only one).
+
+        The result also carries ``baseline_pred`` [B] (``f(baseline)``, the path's first point) and,
+        for a baseline other than zero, ``baseline_x`` / ``baseline_anom`` (the mean over the draws
+        of a random baseline)."""
         model = self.model
         was_training = model.training
         model.eval()
         try:
+            kind = "explicit" if baselines is not None else self.baseline
+            draws = self._draws(batch, kind, baselines)
             if (self.use_graph and target is None and batch.x.is_cuda and _ig_hip(batch.x)
                     and self._cml_path_folded_ok(batch)):
-                return self._attribute_graphed(batch)
-            return self._attribute(batch, target)
+                res = self._attribute_graphed(batch, kind, draws)
+            else:
+                res = self._attribute(batch, target, kind, draws)
+            res["baseline_pred"] = res["path_pred"][0]                  # (a view: no launch)
+            return res
         finally:
             model.train(was_training)
 
+    # -- baselines ---------------------------------------------------------------------
+    def _draws(self, batch, kind: str, baselines=None) -> Optional[List[torch.Tensor]]:
+        """The baselines that are inputs of a call, per interpolated tensor one ``[n, *shape]``
+        stack: the explicit pair (n = 1) or ``n_baselines`` random draws, uniform between each
+        (window, node, channel)'s min and max over the window's T steps. The uniforms come from a
+        CPU ``torch.Generator`` seeded with ``seed`` for every call, in float32 whatever the input's
+        dtype and device: a batch's draws depend on neither the device nor the calls before it. They
+        do depend on the batch's shape and on a window's position in the batch (one tensor of
+        uniforms per input shape): the same window in a batch composed differently gets other draws,
+        and so other attributions.
+        ``None`` for the zero and mean baselines (computed from the inputs where they are used)."""
+        if kind in ("zero", "mean"):
+            return None
+        vals = self._split(batch)[0]
+        if kind == "explicit":
+            if isinstance(baselines, torch.Tensor):
+                baselines = (baselines, None) if vals[0] is batch.x else (None, baselines)
+            given = {id(batch.x): baselines[0], id(batch.anom): baselines[1]}
+            out = []
+            for v in vals:
+                b = given[id(v)]
+                if b is None or tuple(b.shape) != tuple(v.shape):
+                    raise ValueError("baselines must be (xb, ab) with the shapes of batch.x / batch.anom, got "
+                                     f"{None if b is None else tuple(b.shape)} for an input of {tuple(v.shape)}")
+                out.append(b.to(device=v.device, dtype=v.dtype).unsqueeze(0))
+            return out
+        # (every call draws the same uniforms for the same shapes: kept on the device between calls,
+        # n_baselines x the size of the inputs, instead of a host draw and copy per call)
+        key = (self.seed, self.n_baselines, tuple((tuple(v.shape), v.dtype, str(v.device)) for v in vals))
+        if getattr(self, "_uniform_key", None) != key:
+            gen = torch.Generator().manual_seed(self.seed)
+            self._uniforms = [torch.rand((self.n_baselines,) + tuple(v.shape), generator=gen, dtype=torch.float32)
+                              .to(device=v.device, dtype=v.dtype) for v in vals]
+            self._uniform_key = key
+        out = []
+        for v, u in zip(vals, self._uniforms):
+            lo, hi = v.amin(1, keepdim=True), v.amax(1, keepdim=True)
+            d = lo + (hi - lo) * u
+            if v is batch.x:
+                d = d * (batch.node_mask > 0).to(v.dtype)[:, None, :, None]
+            out.append(d)
+        return out
+
+    def first_baseline(self, batch, baselines=None) -> Dict[str, torch.Tensor]:
+        """The baseline the first path of ``attribute(batch, baselines=...)`` starts from, as
+        ``baseline_x`` / ``baseline_anom``: the window mean, the explicit pair, or the first of the
+        random draws (the result's ``baseline_x`` is their mean, a point no path starts from).
+        Empty for the zero baseline."""
+        kind = "explicit" if baselines is not None else self.baseline
+        if kind == "zero":
+            return {}
+        vals = self._split(batch)[0]
+        if kind == "mean":
+            base = [self._window_mean(batch, v) for v in vals]
+        else:
+            base = [d[0] for d in self._draws(batch, kind, baselines)]
+        return {("baseline_x" if v is batch.x else "baseline_anom"): b for v, b in zip(vals, base)}
+
+    @staticmethod
+    def _window_mean(batch, v: torch.Tensor) -> torch.Tensor:
+        """Mean baseline: per (window, node, channel) the mean over the window's T steps, held
+        constant over time; masked nodes stay zero."""
+        m = v.mean(1, keepdim=True).expand_as(v)
+        if v is batch.x:
+            m = m * (batch.node_mask > 0).to(v.dtype)[:, None, :, None]
+        return m.contiguous()
+
     _GRAPH_FIELDS = ("x", "anom", "adj", "node_mask", "anom_pos")
 
-    def _attribute_graphed(self, batch) -> Dict[str, torch.Tensor]:
-        """:meth:`_attribute` captured once per input shape as a HIP graph over static copies of
-        the batch's input tensors, then replayed (inputs copied in, results cloned out)."""
+    def _attribute_graphed(self, batch, kind: str = "zero", draws=None) -> Dict[str, torch.Tensor]:
+        """:meth:`_attribute` captured once per input shape and baseline kind as a HIP graph over
+        static copies of the batch's input tensors, then replayed (inputs copied in, results cloned
+        out). Zero and mean baselines are computed inside the captured region from the static
+        inputs; random draws and explicit baselines are inputs with static buffers of their own."""
         import dataclasses
         ts = [getattr(batch, f) for f in self._GRAPH_FIELDS]
         key = tuple((None if t is None else (tuple(t.shape), t.dtype, str(t.device))) for t in ts)
+        if kind != "zero":
+            key += (kind,) + tuple(tuple(d.shape) for d in (draws or ()))
         # the graph reads the weights and buffers by address: a model whose tensors were replaced
         # (moved, re-created) must be captured again (in-place updates such as load_state_dict or
         # an optimizer step keep the addresses and are seen by the replay)
@@ -153,18 +256,58 @@ class IntegratedGradients:
             self._graph = None
             static = dataclasses.replace(batch, **{f: (None if t is None else t.clone())
                                                    for f, t in zip(self._GRAPH_FIELDS, ts)})
-            g, out = capture_graph(lambda: self._attribute(static, None))
-            # (the record owns the backward seed the capture read by address: an _attribute call of
-            # another shape replaces self._ones, and must not free this one)
-            self._graph = (key, g, static, out, getattr(self, "_ones", None))
-        _, g, static, out = self._graph[:4]
+            sdraws = None if draws is None else [d.clone() for d in draws]
+            g, out = capture_graph(lambda: self._attribute(static, None, kind, sdraws))
+            # (the record owns the backward seed and the baseline buffers the capture read by
+            # address: an _attribute call of another shape replaces self._ones, and must not free
+            # this one)
+            self._graph = (key, g, static, out, getattr(self, "_ones", None), sdraws)
+        _, g, static, out, _, sdraws = self._graph
         for f, t in zip(self._GRAPH_FIELDS, ts):
             if t is not None:
                 getattr(static, f).copy_(t, non_blocking=True)
+        for s, d in zip(sdraws or (), draws or ()):
+            s.copy_(d, non_blocking=True)
         g.replay()
         return {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
-    def _attribute(self, batch, target: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def _attribute(self, batch, target: Optional[torch.Tensor] = None, kind: str = "zero",
+                   draws=None) -> Dict[str, torch.Tensor]:
+        """One path per baseline, averaged over the baselines (the negative-value policy applied to
+        the average); the zero baseline is :meth:`_attribute_one` as it stands."""
+        if kind == "zero":
+            return self._attribute_one(batch, target)
+        vals = self._split(batch)[0]
+        if kind == "mean":
+            bases = [[self._window_mean(batch, v) for v in vals]]
+        else:
+            bases = [[d[i] for d in draws] for i in range(draws[0].shape[0])]
+        if len(bases) == 1:
+            res = self._attribute_one(batch, target, bases[0])
+            mean_base = bases[0]
+        else:
+            parts = [self._attribute_one(batch, target, b, mode=0) for b in bases]
+            res = dict(parts[0])
+            mode = {"keep": 0, "clip": 1, "abs": 2}[self.negative_values]
+            for k in ("grad_x", "grad_anom", "path_pred"):
+                if k not in res:
+                    continue
+                avg = torch.stack([p[k] for p in parts]).mean(0)
+                if k != "path_pred" and mode:
+                    if _ig_hip(avg):
+                        avg = _ops().ig_finalize(avg.contiguous(), avg.new_zeros(0), mode)
+                    else:
+                        avg = avg.abs() if mode == 2 else avg.clamp(min=0)
+                res[k] = avg
+            mean_base = [d.mean(0) for d in draws]
+        for v, b in zip(vals, mean_base):
+            res["baseline_x" if v is batch.x else "baseline_anom"] = b
+        return res
+
+    def _attribute_one(self, batch, target: Optional[torch.Tensor] = None, base=None,
+                       mode: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """One path from ``base`` (a tensor per interpolated input; None: the zero baseline) to the
+        inputs. ``mode`` overrides the negative-value policy (0: keep)."""
         model = self.model
         vals, static, build = self._split(batch)
         B = vals[0].shape[0]
@@ -202,11 +345,13 @@ class IntegratedGradients:
         whole = lean and k >= self.m_steps + 1 and dt == torch.float32
         path_pred = None if whole else torch.empty(self.m_steps + 1, B, device=dev, dtype=dt)
         vf = [v.to(dt).contiguous() for v in vals]
+        bf = None if base is None else [b.to(dt).contiguous() for b in base]
         with _frozen(model), torch.enable_grad():
             for s in (range(0, self.m_steps + 1, k) if fused else ()):
                 # (the first chunk's gradient launch writes the accumulators: no zero fill)
                 self._cml_path_folded_chunk(batch, alphas[s:s + k].contiguous(), wts[s:s + k].contiguous(),
-                                            acc, None if whole else path_pred[s:s + k], target, first=(s == 0 and lean))
+                                            acc, None if whole else path_pred[s:s + k], target, first=(s == 0 and lean),
+                                            base=bf)
                 if whole:
                     path_pred = self._last_y.reshape(self.m_steps + 1, B)
             for s in (range(0, self.m_steps + 1, k) if not fused else ()):
@@ -214,9 +359,17 @@ class IntegratedGradients:
                 kk = a.numel()
                 # zero baseline: x_alpha = alpha * x, folded into the batch dimension (HIP: one
                 # ig_interp launch per input tensor for all kk path points)
+                # (a baseline b: x_alpha = b + alpha (x - b), the alpha = 1 point x itself: ig_interp_base)
                 xs = []
-                for v in vf:
-                    if hip:
+                for j, v in enumerate(vf):
+                    if bf is not None and hip:
+                        xi = _ops().ig_interp_base(v, bf[j], a.contiguous())
+                    elif bf is not None:
+                        shp = (kk,) + (1,) * v.dim()
+                        xi = bf[j] + a.view(shp) * (v - bf[j]).unsqueeze(0)
+                        xi = torch.where(a.view(shp) == 1, v.unsqueeze(0), xi)
+                        xi = xi.reshape((kk * B,) + tuple(v.shape[1:]))
+                    elif hip:
                         xi = _ops().ig_interp(v, a.contiguous())
                     else:
                         shp = (kk,) + (1,) * v.dim()
@@ -234,16 +387,19 @@ class IntegratedGradients:
                     else:
                         g = g.view((kk, B) + tuple(g.shape[1:]))
                         acc[j] += torch.tensordot(w, g.to(dt), dims=1)
-        mode = {"keep": 0, "clip": 1, "abs": 2}[self.negative_values]
+        if mode is None:
+            mode = {"keep": 0, "clip": 1, "abs": 2}[self.negative_values]
+        # x - baseline (the zero baseline: x itself, no launch)
+        df = vf if bf is None else [v - b for v, b in zip(vf, bf)]
         if hip:
             e = vf[0].new_zeros(0)
-            acc = [_ops().ig_finalize(g, v if self.scale_gradients else e, mode) for g, v in zip(acc, vf)]
+            acc = [_ops().ig_finalize(g, v if self.scale_gradients else e, mode) for g, v in zip(acc, df)]
         else:
             if self.scale_gradients:
-                acc = [g * v for g, v in zip(acc, vf)]       # (x - baseline) * avg grad
-            if self.negative_values == "abs":
+                acc = [g * v for g, v in zip(acc, df)]       # (x - baseline) * avg grad
+            if mode == 2:
                 acc = [g.abs() for g in acc]
-            elif self.negative_values == "clip":
+            elif mode == 1:
                 acc = [g.clamp(min=0) for g in acc]
         if pred is None:
             pred = path_pred[-1].float()
@@ -280,10 +436,12 @@ class IntegratedGradients:
         return bool(shape_ok and anom.shape[-1] <= min(F, 4) and not (g.dropout and m.training))
 
     def _cml_path_folded_chunk(self, batch, a: torch.Tensor, wt: torch.Tensor, acc, path_pred_rows,
-                               target: Optional[torch.Tensor], first: bool = False):
+                               target: Optional[torch.Tensor], first: bool = False, base=None):
         """One chunk of path points: GCN forward of all of them (one launch), the TimeLayer + head
         on the path batch, one backward to the LSTM input, then one launch that turns that gradient
-        into the trapezoid-weighted input gradients of x and anom (accumulated into ``acc``)."""
+        into the trapezoid-weighted input gradients of x and anom (accumulated into ``acc``).
+        ``base``: the baseline ``[xb, ab]`` (fp32, contiguous) the path starts from, through the
+        ``_base`` ops; None: the zero baseline."""
         m = self.model
         ops = _ops()
         g = m.gcn_layer
@@ -302,8 +460,13 @@ class IntegratedGradients:
                                      g.bn_moving_mean, g.bn_moving_variance, False, float(g.momentum), float(g.eps))
             Cp = g.kernel.shape[1] + anom.shape[-1]
             Cp += (-Cp) % 4
-            h0 = ops.ig_gcn_pool_fwd(x, w, anom, g.kernel.contiguous(), g.bias.contiguous(), st[2].contiguous(),
-                                     st[3].contiguous(), g.prelu_alpha.contiguous(), a, int(Cp))
+            if base is None:
+                h0 = ops.ig_gcn_pool_fwd(x, w, anom, g.kernel.contiguous(), g.bias.contiguous(), st[2].contiguous(),
+                                         st[3].contiguous(), g.prelu_alpha.contiguous(), a, int(Cp))
+            else:
+                h0 = ops.ig_gcn_pool_fwd_base(x, base[0], w, anom, base[1], g.kernel.contiguous(),
+                                              g.bias.contiguous(), st[2].contiguous(), st[3].contiguous(),
+                                              g.prelu_alpha.contiguous(), a, int(Cp))
         h0.requires_grad_(True)
         spec = m.head_spec()
         taken = []
@@ -354,9 +517,14 @@ class IntegratedGradients:
             self._last_y = y.detach()
         else:
             path_pred_rows.copy_(y.detach().view(kk, B).to(path_pred_rows.dtype))
-        ops.ig_gcn_pool_bwd(x, w, mask, gh.contiguous(), g.kernel.contiguous(), g.bias.contiguous(),
-                            st[2].contiguous(), st[3].contiguous(), g.prelu_alpha.contiguous(), a, wt.float(),
-                            acc[0], acc[1], bool(first))
+        if base is None:
+            ops.ig_gcn_pool_bwd(x, w, mask, gh.contiguous(), g.kernel.contiguous(), g.bias.contiguous(),
+                                st[2].contiguous(), st[3].contiguous(), g.prelu_alpha.contiguous(), a, wt.float(),
+                                acc[0], acc[1], bool(first))
+        else:
+            ops.ig_gcn_pool_bwd_base(x, base[0], w, mask, gh.contiguous(), g.kernel.contiguous(),
+                                     g.bias.contiguous(), st[2].contiguous(), st[3].contiguous(),
+                                     g.prelu_alpha.contiguous(), a, wt.float(), acc[0], acc[1], bool(first))
 
 
 def completeness_gap(ig_res: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -516,6 +684,8 @@ class IntegratedGradientsExplainer:
             bids = bids[:max_batches]
         engine = IntegratedGradients(self.model, self.ds_type, m_steps=int(self.ig_cfg.m_steps),
                                      baseline=self.ig_cfg.get("baseline", "zero"),
+                                     n_baselines=int(self.ig_cfg.get("n_baselines", 8)),
+                                     seed=int(self.ig_cfg.get("random_seed", 42)),
                                      scale_gradients=bool(self.ig_cfg.get("scale_gradients", True)),
                                      negative_values=self.ig_cfg.get("negative_values", "keep"),
                                      max_rows=int(self.ig_cfg.get("max_rows", 16384)))
@@ -524,7 +694,7 @@ class IntegratedGradientsExplainer:
             if not self.ig_cfg.get("load_gradients_from_sample_file", False):
                 res = engine.attribute(batch)
                 if self.ig_cfg.get("plot_interpolated_data_element_series", False):
-                    self._plot_interpolated(batch, bid, int(self.ig_cfg.m_steps))
+                    self._plot_interpolated(batch, bid, int(self.ig_cfg.m_steps), engine.first_baseline(batch))
             else:
                 with torch.no_grad():
                     res = {"pred": self.model(batch.model_inputs(self.ds_type, self.is_baseline)).reshape(
@@ -532,21 +702,31 @@ class IntegratedGradientsExplainer:
             self._unwrap_and_save(bid, batch, ids, res)
         return self.results
 
-    def _plot_interpolated(self, batch, bid: int, m: int):
-        """The batch's first sample along the zero-baseline path x_a = a x (``_interpolate`` +
-        ``_plot_interpolated_data_element_series``, ``integrated_gradients.py:919-942,1415-1466``):
-        ``interpolated_data_element_1_batch_<id>.png`` (flagged series) and ``..._2_..`` (node
-        features) in the output directory."""
+    def _plot_interpolated(self, batch, bid: int, m: int, res=None):
+        """The batch's first sample along the path x_a = b + a (x - b) from the baseline the
+        attribution started from (``res``: ``baseline_x`` / ``baseline_anom`` of
+        :meth:`IntegratedGradients.first_baseline`, for a random baseline the first of its draws;
+        absent: the zero baseline, x_a = a x) (``_interpolate`` + ``_plot_interpolated_data_element_series``,
+        ``integrated_gradients.py:919-942,1415-1466``): ``interpolated_data_element_1_batch_<id>.png``
+        (flagged series) and ``..._2_..`` (node features) in the output directory."""
         from ..viz.ig import plot_interpolated_series
         alphas = np.linspace(0.0, 1.0, m + 1)
+        res = res or {}
+
+        def first(key, like):
+            b = res.get(key)
+            return np.zeros_like(like) if b is None else b[0].detach().float().cpu().numpy()
+
         out = []
         if batch.anom is not None:
             a0 = batch.anom[0].detach().float().cpu().numpy()
-            out.append(plot_interpolated_series(alphas[:, None, None] * a0[None], alphas,
+            b0 = first("baseline_anom", a0)
+            out.append(plot_interpolated_series(b0[None] + alphas[:, None, None] * (a0 - b0)[None], alphas,
                                                 os.path.join(self.output_dir,
                                                              f"interpolated_data_element_1_batch_{bid}.png")))
-        x0 = batch.x[0].detach().float().cpu().numpy().transpose(1, 0, 2)          # [N, T, C]
-        out.append(plot_interpolated_series(alphas[:, None, None, None] * x0[None], alphas,
+        x0 = batch.x[0].detach().float().cpu().numpy()
+        x0, b0 = x0.transpose(1, 0, 2), first("baseline_x", x0).transpose(1, 0, 2)      # [N, T, C]
+        out.append(plot_interpolated_series(b0[None] + alphas[:, None, None, None] * (x0 - b0)[None], alphas,
                                             os.path.join(self.output_dir, f"interpolated_data_element_2_batch_{bid}.png")))
         return out
 
@@ -587,6 +767,9 @@ class IntegratedGradientsExplainer:
         anom = batch.anom.detach().float().cpu().numpy() if batch.anom is not None else None
         gx = res["grad_x"].detach().cpu().numpy() if "grad_x" in res else None
         ga = res["grad_anom"].detach().cpu().numpy() if "grad_anom" in res else None
+        # (a baseline other than zero: saved next to the inputs it is the reference point of)
+        bx = res["baseline_x"].detach().float().cpu().numpy() if "baseline_x" in res else None
+        ba = res["baseline_anom"].detach().float().cpu().numpy() if "baseline_anom" in res else None
         for i in keep:
             sensor, date = self._sample_info(int(ids[i]))
             tr, pr = int(true[i]), int(pred_cls[i])
@@ -603,6 +786,10 @@ class IntegratedGradientsExplainer:
                 files["gradients_features_unwrapped"] = gx[i][:, nodes].transpose(1, 0, 2)
             if ga is not None:
                 files["gradients_anom_ts_unwrapped"] = ga[i]
+            if bx is not None:
+                files["baseline_features_unwrapped"] = bx[i][:, nodes].transpose(1, 0, 2)
+            if ba is not None:
+                files["baseline_anom_ts_unwrapped"] = ba[i]
             if "path_pred" in res:
                 files["path_predictions_unwrapped"] = res["path_pred"][:, i].detach().cpu().numpy()
             if self.ig_cfg.get("load_gradients_from_sample_file", False):
@@ -653,6 +840,10 @@ def run_explainer(args):
     pc, mc = load_configs(args)
     dev = resolve_device(args.device)
     xc = C.load(args.xai_config) if args.xai_config else C.default("xai_ig")
+    # --set xai.<key>=v, or integrated_gradients.<key>=v (e.g. integrated_gradients.baseline=mean)
+    ov = getattr(args, "overrides", None) or []
+    C.parse_overrides(xc, [o[len("xai."):] for o in ov if o.startswith("xai.")]
+                      + [o for o in ov if o.startswith("integrated_gradients.")])
     if args.out_dir:
         xc["output_dir"] = args.out_dir
     mc["model_path"] = args.model_dir

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Integrated-gradients throughput (BASELINE config v): explained windows/s for the CML GCN.
 
-    python scripts/bench_ig.py [--batches K] [--m-steps 100] [--batch 128]
+    python scripts/bench_ig.py [--batches K] [--m-steps 100] [--batch 128] [--baseline zero|mean|random]
+                               [--generic-route]
     torchrun --nproc-per-node N scripts/bench_ig.py ...     (batches sharded over ranks)
 
 Each explained window costs m_steps + 1 forward + backward passes (reference
@@ -31,6 +32,11 @@ def main(argv=None):
                     "(324 = one full 32768-row path chunk)")
     ap.add_argument("--m-steps", type=int, default=100)
     ap.add_argument("--max-rows", type=int, default=32768, help="path rows (windows x path points) per pass")
+    ap.add_argument("--baseline", default="zero", choices=["zero", "mean", "random"],
+                    help="baseline the paths start from (gnnqc.xai.ig.IntegratedGradients)")
+    ap.add_argument("--n-baselines", type=int, default=8, help="draws of the random baseline")
+    ap.add_argument("--generic-route", action="store_true",
+                    help="refuse the path-folded kernels: kk x B interpolated copies through the model (A/B)")
     args = ap.parse_args(argv)
 
     from gnnqc import config as C
@@ -50,7 +56,10 @@ def main(argv=None):
     store = DeviceStore(ws, "rolling_median", pc.graph, device=dev)
     model = GCNClassifier(mc, pc).to(dev)
     D.broadcast_module(model)
-    ig = IntegratedGradients(model, "cml", m_steps=args.m_steps, max_rows=args.max_rows)
+    if args.generic_route:
+        IntegratedGradients._cml_path_folded_ok = lambda self, batch: False
+    ig = IntegratedGradients(model, "cml", m_steps=args.m_steps, max_rows=args.max_rows, baseline=args.baseline,
+                             n_baselines=args.n_baselines)
     n = store.n_windows
     B = args.batch
 
@@ -78,6 +87,7 @@ def main(argv=None):
         print(json.dumps({
             "metric": "integrated-gradients explained windows/s, CML GCN", "value": round(windows / dt, 2),
             "unit": "windows/s (whole job)", "n_gpus": world, "m_steps": args.m_steps,
+            "baseline": args.baseline, "route": "generic" if args.generic_route else "path-folded",
             "passes_per_window": args.m_steps + 1, "batch": B, "ms_per_batch": round(1e3 * dt / args.batches, 3),
             "completeness_gap_max": gap, "dtype": "bf16", "data": "synthetic CML (23 links x 28 days), random init",
         }), flush=True)
