@@ -10,8 +10,12 @@ forward   z_t = bf16(x_t) bf16(W) + bf16(h_{t-1}) bf16(U) + b; gates / c / h in 
           the gates saved for the backward are bf16 for H <= 64 (the time-major kernels pack
           them, ``lstm_tm_common.h gates_pack``) and full precision for H = 128 (the training
           chain's time4; the standalone time4 layer and lstm_fwd<128> save bf16 gates as well -
-          a difference well inside the tests' tolerances); the recompute-gates layers (lstm_tm.hip RG)
-          save c_t in bf16 (TM_RG_BF16C), likewise not modelled here;
+          a difference well inside the tests' tolerances);
+          ``saved="rg"`` models the recompute-gates layers instead (lstm_tm.hip RG): their backward
+          recomputes the gates in fp32 from the same bf16 operands (no gate rounding) and reads c_t
+          and c_{t-1} back from bf16 (TM_RG_BF16C), so tanh(c_t) and c_{t-1} come from bf16(c). A
+          pair's layer-A h saved in bf16 (TM_RG_BF16H) needs no modelling: its only readers take h
+          as a bf16 MFMA operand, which this reference rounds anyway;
 backward  dz_t (the four gate pre-activation gradients, from the saved gates) is rounded to
           bf16 - the value the kernels store and feed to every MFMA; dh_{t-1} = dz_t bf16(U)^T,
           dx = dz bf16(W)^T, dW = bf16(x)^T dz, dU = bf16(h_{t-1})^T dz, db = sum dz.
@@ -59,7 +63,9 @@ class KernelLSTM(torch.autograd.Function):
     """x [M, T, Din], W [Din, 4H], U [H, 4H], b [4H] -> h [M, T, H] (or the last step [M, H])."""
 
     @staticmethod
-    def forward(ctx, x, W, U, b, return_sequences: bool, rounding: bool = True):
+    def forward(ctx, x, W, U, b, return_sequences: bool, rounding: bool = True, saved: str = "gates_bf16"):
+        if saved not in ("gates_bf16", "rg"):
+            raise ValueError(f"saved must be 'gates_bf16' or 'rg', not {saved!r}")
         r = _bf if rounding else _same
         M, T, _ = x.shape
         H = U.shape[0]
@@ -80,9 +86,12 @@ class KernelLSTM(torch.autograd.Function):
             gs.append(torch.cat([i, f, g, o], -1))
         hseq = torch.stack(hs, 1)
         gates = torch.stack(gs, 1)
-        if rounding and H <= 64:
+        cseq = torch.stack(cs, 1)
+        if saved == "rg":
+            cseq = r(cseq)                          # recomputed (unrounded) gates, c read back from bf16
+        elif rounding and H <= 64:
             gates = _bf(gates)                      # the time-major kernels save bf16 gates
-        ctx.save_for_backward(xr, Wr, Ur, hseq, torch.stack(cs, 1), gates)
+        ctx.save_for_backward(xr, Wr, Ur, hseq, cseq, gates)
         ctx.return_sequences = return_sequences
         ctx.rounding = rounding
         return hseq if return_sequences else hseq[:, -1]
@@ -116,7 +125,7 @@ class KernelLSTM(torch.autograd.Function):
         dW = torch.einsum("mtd,mtg->dg", xr, dz)
         dU = torch.einsum("mth,mtg->hg", r(hprev), dz)
         db = dz.sum((0, 1))
-        return dx, dW, dU, db, None, None
+        return dx, dW, dU, db, None, None, None
 
 
 __all__ = ["KernelLSTM", "kernel_rounding", "kernel_rounding_on"]

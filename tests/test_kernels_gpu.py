@@ -355,7 +355,8 @@ def test_gcn_pool_weights_matches_eager(cuda_device, aggregate, pooling):
 def test_lstm_time_major_fused_bwd_matches_eager(cuda_device, H, Din, ret_seq, wgrad, in_rec, monkeypatch):
     """lstm_tm_fwd / lstm_tm_bwd (recurrence + dx + fused dW/dU/db) vs fp64 eager. in_rec: the
     weight gradients inside the recurrence (lstm_tm_bwd_wg_kernel, H <= 32 with float4 x
-    granules), else the separate weight-gradient pass."""
+    granules), else the separate weight-gradient pass.
+    (Sharp bounds against the rounding-aware oracle, per branch: tests/test_lstm_tm_kernels_gpu.py.)"""
     from gnnqc.ops.lstm import lstm_eager, lstm_layer_tm, tm_eligible
     if in_rec and not (wgrad and H <= 32 and Din % 4 == 0):
         pytest.skip("the in-recurrence weight gradients take H <= 32, Din % 4 == 0")
@@ -394,7 +395,8 @@ def test_lstm_time_major_fused_bwd_matches_eager(cuda_device, H, Din, ret_seq, w
 def test_lstm_tm_recomputed_gates_match_saved_gates(cuda_device, monkeypatch, H, Din, wgrad, pair):
     """Recompute-gates backward (lstm_tm.hip RG: the forward saves only c, the backward recomputes
     i, f, g, o from x_t and h_{t-1}) vs the saved-gates form: identical forward output, gradients
-    within bf16-gate rounding of each other, and the RG gradients against an fp64 eager oracle."""
+    within bf16-gate rounding of each other, and the RG gradients against an fp64 eager oracle.
+    (Sharp bounds against the rounding-aware oracle, per branch: tests/test_lstm_tm_kernels_gpu.py.)"""
     from gnnqc.ops import lstm as L
     from gnnqc.utils.native import hip_ops
     monkeypatch.setattr(L._Pipe, "enabled", False)      # (training layers of any size take RG)
@@ -588,7 +590,8 @@ def test_timelayer_cnn_branch_hip_vs_eager(cuda_device, monkeypatch):
 @pytest.mark.parametrize("in_rec", [False, True])
 def test_lstm_time_major_padded_channels(cuda_device, H, wgrad, in_rec, monkeypatch):
     """x with zero channels past W's rows (19 -> 20, float4 loader granules) == unpadded eager;
-    in_rec: weight gradients inside the recurrence (the bias row sits inside the last x granule)."""
+    in_rec: weight gradients inside the recurrence (the bias row sits inside the last x granule).
+    (Sharp bounds against the rounding-aware oracle, per branch: tests/test_lstm_tm_kernels_gpu.py.)"""
     from gnnqc.ops.lstm import lstm_eager, lstm_layer_tm
     if in_rec and not wgrad:
         pytest.skip("in-recurrence weight gradients need wgrad")
