@@ -63,7 +63,7 @@ inline bool& deterministic_mode() {
 // Deferred weight-gradient reductions (direct-accumulation training steps whose layers run the
 // per-layer backward, e.g. SoilNet's 418-tile recurrences): while set, lstm_grads_rows queues its
 // split reduction (workspace + destination buffers) instead of launching it, and
-// lstm_reduce_flush (lstm_tm.hip) runs every queued one in ONE launch at the end of the backward.
+// lstm_reduce_flush (lstm_grads_jobs.hip) runs every queued one in ONE launch at the end of the backward.
 // Set per call by gnnqc.ops.lstm, only when the gradient buffers are the optimiser's own.
 inline bool& defer_reduce_mode() {
   static bool v = false;
@@ -77,6 +77,11 @@ struct DeferredRed {
   float* db;
 };
 std::vector<DeferredRed>& deferred_reds();      // lstm_grads.hip
+
+// host functions of one kernel file that others call
+int* chain_ctl(int dev);   // lstm_chain.hip: the device's chain control words ([4] / [5] head tickets, [7] a gradient
+                           // producer saw a non-finite value)
+at::Tensor maxpool1d_bwd(const at::Tensor& dy, const at::Tensor& idx, int64_t T, int64_t p);   // pool.hip
 
 #define GQ_CHECK(cond, msg) TORCH_CHECK(cond, "gnnqc: ", msg)
 #define GQ_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); TORCH_CHECK(e__ == hipSuccess, "gnnqc kernel launch failed: ", hipGetErrorString(e__)); } while (0)

@@ -1,5 +1,5 @@
 // Device-side pieces of the fused CML GCN (gcn_fused.hip) shared with the LSTM weight-gradient
-// launch (lstm_tm.hip lstm_grads_multi), which runs the GCN backward as extra workgroups: the two
+// launch (lstm_grads_jobs.hip lstm_grads_multi), which runs the GCN backward as extra workgroups: the two
 // are independent (both only need the chain backward's outputs), and one launch of both overlaps
 // them on the otherwise idle CUs instead of running them back to back.
 #pragma once
@@ -8,8 +8,6 @@
 #include <vector>
 
 namespace gq {
-
-int* chain_ctl(int dev);   // lstm_chain.hip: word 7 = a gradient producer saw a non-finite value
 
 constexpr int GF_MAX_CIN = 4;
 constexpr int GF_ROW_MAX = 128;        // N * Cin floats per staged row
@@ -747,5 +745,17 @@ __device__ __forceinline__ void gcn_coef_bwd_body(const GcnCoefJob& J, int bx) {
   for (int a = 0; a < NA; ++a) tot[a] = (red[0][a][f] + red[1][a][f]) + (red[2][a][f] + red[3][a][f]);
   gcn_bwd_apply<Cin, F>(tot, f, J.Sg, J.st, J.W, J.bias, J.dW, J.dgamma, J.dbeta, J.dalpha, J.nf);
 }
+
+// gcn_fused.hip (host): the two backward forms as job records, for its own launches and for lstm_grads_multi
+GcnBwdJob gcn_bwd_job(const at::Tensor& dh, int64_t c_off, const at::Tensor& series, const at::Tensor& shift,
+                      const at::Tensor& scale, const at::Tensor& win_group, const at::Tensor& win_center,
+                      const at::Tensor& win_valid, const at::Tensor& group_anom_pos, const at::Tensor& pw,
+                      const at::Tensor& wids, const at::Tensor& table, const c10::optional<at::Tensor>& cursor,
+                      int64_t tb, int64_t seq_len, bool time_norm, const at::Tensor& S, const at::Tensor& st,
+                      const at::Tensor& W, const at::Tensor& bias, const at::Tensor& alpha, const at::Tensor& dW,
+                      const at::Tensor& dgamma, const at::Tensor& dbeta, const at::Tensor& dalpha, int& nblocks);
+GcnCoefJob gcn_coef_job(const at::Tensor& dh, int64_t c_off, const at::Tensor& coef, const at::Tensor& S,
+                        const at::Tensor& st, const at::Tensor& W, const at::Tensor& bias, const at::Tensor& dW,
+                        const at::Tensor& dgamma, const at::Tensor& dbeta, const at::Tensor& dalpha);
 
 }  // namespace gq

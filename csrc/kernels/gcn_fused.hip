@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256) void gcn_fused_fwd_kernel(
 }
 
 // ---- backward (training): grid (B, NY), 256 threads (body in gcn_fused.h: it also runs as extra
-// workgroups of the LSTM weight-gradient launch, lstm_tm.hip lstm_grads_multi)
+// workgroups of the LSTM weight-gradient launch, lstm_grads_jobs.hip lstm_grads_multi)
 template <int Cin, int F>
 __global__ __launch_bounds__(256) void gcn_fused_bwd_kernel(GcnBwdJob J) {
   __shared__ __attribute__((aligned(16))) char smem[GcnBwdLds<Cin, F>::BYTES];
@@ -647,7 +647,7 @@ bool gcn_coef_flush(const at::Tensor& like) {
 
 // The training backward's job (gcn_fused_bwd_body): adds dW, dgamma, dbeta, dalpha (float atomics)
 // from dh [T, Mp, Dh] channels [c_off, c_off + F). (db is zero in training: BatchNorm removes the
-// bias.) nblocks = B * ny workgroups (0: nothing to do). Shared with lstm_grads_multi (lstm_tm.hip).
+// bias.) nblocks = B * ny workgroups (0: nothing to do). Shared with lstm_grads_multi (lstm_grads_jobs.hip).
 GcnBwdJob gcn_bwd_job(const at::Tensor& dh, int64_t c_off, const at::Tensor& series, const at::Tensor& shift,
                       const at::Tensor& scale, const at::Tensor& win_group, const at::Tensor& win_center,
                       const at::Tensor& win_valid, const at::Tensor& group_anom_pos, const at::Tensor& pw,

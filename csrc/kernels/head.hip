@@ -22,7 +22,6 @@
 
 namespace gq {
 
-int* chain_ctl(int dev);   // lstm_chain.hip: the device's chain control words
 
 constexpr int HT = 16;     // rows per tile: 8 workgroups for a CML batch of 128 (LDS-bound loops
                            // spread over 8 CUs; 64-row tiles left 2 CUs doing 4x the work each)

@@ -1,6 +1,6 @@
 // Cross-CU layer pipeline for the forward of a time-major LSTM stack (gfx950).
 //
-// The per-layer forward kernels (lstm_tm.hip) run one after another: with the CML batch a
+// The per-layer forward kernels (lstm_tm_fwd.hip) run one after another: with the CML batch a
 // recurrence occupies 8 of the 256 CUs, and the stack's six recurrences (plus three pool
 // launches) are a serial sum. Sequences never mix across layers, so tile j of layer k+1
 // only needs tile j of layer k - and only up to the step it is at. This kernel runs all
@@ -1050,7 +1050,7 @@ struct ChainBArgs {
 static_assert(sizeof(ChainBArgs) <= 4096, "chain backward kernel arguments");
 
 // LDS pitches of the backward stages (bf16 dz rows G4 + ZPAD, fp32 dx rows 32 KX + XPAD), chosen with
-// scripts/lds_model as in lstm_tm.hip's backward: with a 32-float dx pitch the dx wave's dx^T stores
+// scripts/lds_model as in lstm_tm_bwd_body.h: with a 32-float dx pitch the dx wave's dx^T stores
 // (16 sequences x 4 quads per wave) fell on 2 banks of ds_write_b32's 32 (16-way); 33 leaves 2-way
 #ifndef CHAINB_ZPAD
 #define CHAINB_ZPAD 16

@@ -22,8 +22,6 @@
 
 namespace gq {
 
-int* chain_ctl(int dev);   // lstm_chain.hip: the device's chain control words
-
 std::vector<DeferredRed>& deferred_reds() {
   static std::vector<DeferredRed> v;
   return v;
@@ -85,9 +83,6 @@ void launch_grads_h(int DT, int grx, dim3 grid, hipStream_t st, const void* dz, 
   }
 }
 
-void lstm_grads_reduce_records(const at::Tensor& ws_t, int H, int Din, int splits, float* dW, float* dU, float* db,
-                               hipStream_t st);
-
 // Flat-row launcher shared by the sequence-major (lstm_grads) and time-major (lstm_tm_bwd)
 // paths: row r of dz / x / dx has h_{t-1} at row r - hshift when r % period >= hshift.
 // x rows have pitch ldx, dx rows pitch lddx; only the first Din (= rows of W) channels are used.
@@ -97,7 +92,8 @@ void lstm_grads_rows(const void* dz, int zbf, const float* x, const float* hseq,
                      long dx_cb_stride, int lddx, long x_elems, hipStream_t st) {
   if (rows == 0) return;
   TORCH_CHECK(ldx >= Din && ldx <= 144, "gnnqc lstm_grads: x row pitch ", ldx, " (Din ", Din, ")");
-  const int ncb = (4 * H) / GR_CB;
+  const GradsGeom geo(H, Din);
+  const int ncb = geo.ncb, DT = geo.DT;
   const long ntiles = (rows + GR_ROWS - 1) / GR_ROWS;
   // ~2 tiles per workgroup for small row counts (latency: everything in flight at once),
   // ~2 workgroups per CU for large ones: each split writes a (DT + HT) x 4H record that the
@@ -110,16 +106,11 @@ void lstm_grads_rows(const void* dz, int zbf, const float* x, const float* hseq,
     return e != nullptr ? std::max(256, std::atoi(e)) : 512;
   }();
   const int splits = (int)std::max<long>(1, std::min<long>((ntiles + 1) / 2, std::max(64, wg_budget / ncb)));
-  const int DT = (Din + 1 + 15) / 16;
-  const int HT = H / 16;
   const int grx = (ldx % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0) ? 4 : 1;
   const int xg = (int)((GR_ROWS * (long)ldx / grx + 255) / 256);
-  const int RC = (DT + HT) * 1024 * ncb;          // floats per split record (all column blocks)
-  const int NG = std::max(1, splits / 512);       // split groups of the reduction
-  auto ws_t = at::empty({(long)splits * RC + (NG > 1 ? (long)NG * RC : 0L)},
+  auto ws_t = at::empty({geo.ws_floats(splits)},
                         at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, c10::hip::current_device()));
   float* ws = ws_t.data_ptr<float>();
-  float* ws2 = ws + (size_t)splits * RC;
   dim3 grid(ncb, splits);
 #define GQ_GR_H(HH)                                                                                              \
   case HH:                                                                                                       \
@@ -144,27 +135,24 @@ void lstm_grads_rows(const void* dz, int zbf, const float* x, const float* hseq,
 // mode, else one reduce launch (+ the group-sum launch).
 void lstm_grads_reduce_records(const at::Tensor& ws_t, int H, int Din, int splits, float* dW, float* dU, float* db,
                                hipStream_t st) {
-  const int ncb = (4 * H) / GR_CB;
-  const int DT = (Din + 1 + 15) / 16;
-  const int HT = H / 16;
-  const int RC = (DT + HT) * 1024 * ncb;
-  const int NG = std::max(1, splits / 512);
-  TORCH_CHECK(ws_t.numel() >= (long)splits * RC + (NG > 1 ? (long)NG * RC : 0L), "lstm_grads: split records");
+  const GradsGeom geo(H, Din);
+  const int NG = GradsGeom::groups(splits);
+  TORCH_CHECK(ws_t.numel() >= geo.ws_floats(splits), "lstm_grads: split records");
   if (defer_reduce_mode()) {                      // summed by lstm_reduce_flush with the other layers'
     deferred_reds().push_back(DeferredRed{ws_t, H, Din, splits, dW, dU, db});
     return;
   }
-  float* ws = ws_t.data_ptr<float>();
-  float* ws2 = ws + (size_t)splits * RC;
   // every weight-gradient reduction raises the non-finite flag (chain control word 7) that the
   // flag-driven Adam (adam_flagged) decides from
-  int* nf = chain_ctl(c10::hip::current_device()) + 7;
-  hipLaunchKernelGGL(lstm_grads_reduce_kernel, dim3((RC + 15) / 16, NG), dim3(256), 0, st, ws, splits, RC, ws2, ncb,
-                     DT, HT, Din, H, dW, db, dU, nf);
+  const RedJob r = make_red_job(ws_t.data_ptr<float>(), H, Din, splits, dW, dU, db,
+                                chain_ctl(c10::hip::current_device()) + 7);
+  float* ws2 = ws_t.data_ptr<float>() + (size_t)splits * r.RC;
+  hipLaunchKernelGGL(lstm_grads_reduce_kernel, dim3((r.RC + 15) / 16, NG), dim3(256), 0, st, r.ws, splits, r.RC, ws2,
+                     r.ncb, r.DT, r.HT, Din, H, dW, db, dU, r.nf);
   GQ_LAUNCH_CHECK();
   if (NG > 1) {
-    hipLaunchKernelGGL(lstm_grads_reduce_final_kernel, dim3(std::min((RC + 255) / 256, 1024)), dim3(256), 0, st, ws2,
-                       NG, RC, ncb, DT, HT, Din, H, dW, db, dU, nf);
+    hipLaunchKernelGGL(lstm_grads_reduce_final_kernel, dim3(std::min((r.RC + 255) / 256, 1024)), dim3(256), 0, st, ws2,
+                       NG, r.RC, r.ncb, r.DT, r.HT, Din, H, dW, db, dU, r.nf);
     GQ_LAUNCH_CHECK();
   }
 }
@@ -286,11 +274,9 @@ at::Tensor lstm_dx(const at::Tensor& dz, const at::Tensor& W, const at::Tensor& 
   return dx;
 }
 
-int lstm_grads_col_blocks(int H) { return (4 * H) / GR_CB; }
-
 // (A one-pass dx = dz W^T over all 4H gate-units instead of ncb slabs + their sum was measured
 // slower on the SoilNet step - 5.016 vs 4.944 ms - and removed; the time-major layers now take dx
-// from their recurrence instead, lstm_tm.hip tm_rec_dx.)
+// from their recurrence instead, lstm_tm_bwd.hip, tm_rec_dx.)
 
 // dz [M(p),T,4H] from lstm_bwd; x [M,T,Din] (unit inner stride, row stride ldx);
 // hseq [M,T,H]; W [Din,4H]. dW/dU/db are ACCUMULATED into (pass zeroed or existing

@@ -1,5 +1,6 @@
 // Device bodies of the LSTM weight-gradient pass (lstm_grads.hip) and its split reduction,
-// shared with lstm_tm.hip, whose backward launches can carry them as extra workgroups.
+// shared with lstm_grads_jobs.hip, whose launches carry them as extra workgroups of a recurrence or batch them,
+// and the host-side record geometry (GradsGeom, make_grad_job, make_red_job) every launcher of them uses.
 #pragma once
 #include "common.h"
 
@@ -39,6 +40,92 @@ struct RedJob {
   int* nf;                // non-finite gradient flag (chain control word 7, read by adam_flagged)
   int splits, RC, ncb, DT, HT, Din, H, nblocks, kb;
 };
+
+// ---- host side: the record geometry, said once
+constexpr int lstm_grads_col_blocks(int H) { return (4 * H) / GR_CB; }
+constexpr int GR_GROUP_SPLITS = 512;    // split records per reduction group
+constexpr int PIPE_MAX_SPLITS = GR_GROUP_SPLITS;   // a job's records are one reduction group: its reduce fits one launch
+constexpr int PIPE_RED_KB = 8;          // slot blocks per workgroup of a job's wide reduction (lstm_grads_reduce_multi)
+
+// A layer's split record: [column block][DT din tiles (incl. the bias row) + HT k tiles][4 waves][64 lanes][4]
+struct GradsGeom {
+  int DT, HT, ncb, RC;                  // RC: floats per split record (all column blocks)
+  static constexpr int din_tiles(int Dw) { return (Dw + 1 + 15) / 16; }
+  constexpr GradsGeom(int H, int Dw)
+      : DT(din_tiles(Dw)), HT(H / 16), ncb(lstm_grads_col_blocks(H)), RC((DT + HT) * 1024 * ncb) {}
+  static constexpr int groups(int splits) { return splits / GR_GROUP_SPLITS > 1 ? splits / GR_GROUP_SPLITS : 1; }
+  // workspace floats of `splits` records, plus the group sums when there are several reduction groups
+  constexpr long ws_floats(int splits) const {
+    return (long)splits * RC + (groups(splits) > 1 ? (long)groups(splits) * RC : 0L);
+  }
+  // records of a job workspace: exactly 1 .. PIPE_MAX_SPLITS of them (`what`: the caller's message)
+  int job_splits(const at::Tensor& ws, const char* what) const {
+    const int splits = (int)(ws.numel() / RC);
+    TORCH_CHECK(splits >= 1 && splits <= PIPE_MAX_SPLITS && ws.numel() == (long)splits * RC, what);
+    return splits;
+  }
+};
+
+// lstm_grads.hip: weight gradients (+ dx) over flat rows, h_{t-1} hshift rows back; the reduction of split
+// records; dx = dz W^T on its own
+void lstm_grads_rows(const void* dz, int zbf, const float* x, const float* hseq, const float* W, float* dx, float* dW,
+                     float* dU, float* db, long rows, long period, long hshift, int H, int Din, int ldx,
+                     long dx_cb_stride, int lddx, long x_elems, hipStream_t st);
+void lstm_grads_reduce_records(const at::Tensor& ws_t, int H, int Din, int splits, float* dW, float* dU, float* db,
+                               hipStream_t st);
+void lstm_dx_rows(const void* dz, int zbf, const float* W, float* dx, long rows, int H, int Dw, int lddx,
+                  hipStream_t st);
+
+// A weight-gradient pass over the rows of x (unit inner stride, 16-byte aligned rows of pitch ldx) as a job
+// record. dz is bf16 (job_dz); ws holds exactly `splits` records.
+inline GradJob make_grad_job(const at::Tensor& dz, const at::Tensor& x, const at::Tensor& h, const at::Tensor& W,
+                             long period, long hshift, const at::Tensor& ws, const char* what) {
+  const int H = (int)W.size(1) / 4, Dw = (int)W.size(0);
+  const GradsGeom g(H, Dw);
+  GradJob j{};
+  j.dz = dz.data_ptr();
+  j.x = x.data_ptr<float>();
+  j.h = h.data_ptr<float>();
+  j.W = W.data_ptr<float>();
+  j.ws = ws.data_ptr<float>();
+  j.ldx = (int)x.stride(-2);
+  j.rows = x.numel() / x.size(-1);
+  j.period = period;
+  j.hshift = hshift;
+  j.x_elems = (long)(x.storage().nbytes() / sizeof(float)) - x.storage_offset();
+  j.Din = Dw;
+  j.xg = (int)((32L * j.ldx / 4 + 255) / 256);
+  j.ncb = g.ncb;
+  j.splits = g.job_splits(ws, what);
+  j.nblocks = j.ncb * j.splits;
+  return j;
+}
+
+// job bodies read bf16 dz: an fp32 one (sequence-major lstm_bwd) is rounded here exactly as the grads body
+// would round it when staging, so the result is the same
+inline at::Tensor job_dz(const at::Tensor& dz) { return dz_bf16(dz) ? dz : dz.to(at::kBFloat16); }
+
+// The reduction of `splits` records into dW / dU / db as a job record, with the rule for its grid: the wide
+// form (PIPE_RED_KB slot blocks per workgroup) once one block per 16 slots would exceed a few waves of workgroups
+inline RedJob make_red_job(const float* ws, int H, int Dw, int splits, float* dW, float* dU, float* db, int* nf) {
+  const GradsGeom g(H, Dw);
+  RedJob r{};
+  r.ws = ws;
+  r.dW = dW;
+  r.dU = dU;
+  r.db = db;
+  r.nf = nf;
+  r.splits = splits;
+  r.RC = g.RC;
+  r.ncb = g.ncb;
+  r.DT = g.DT;
+  r.HT = g.HT;
+  r.Din = Dw;
+  r.H = H;
+  r.kb = (g.RC + 15) / 16 > 1024 ? PIPE_RED_KB : 1;
+  r.nblocks = (g.RC + 16 * r.kb - 1) / (16 * r.kb);
+  return r;
+}
 
 // One workgroup = (column block cb of 64 gate-units, row split s); it walks the row tiles
 // s, s + splits, ... with a one-tile register prefetch: tile i+1's dz / x / h_{t-1} loads are

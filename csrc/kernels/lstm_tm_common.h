@@ -1,10 +1,105 @@
-// Pieces shared by the time-major LSTM kernels (lstm_tm.hip, lstm_chain.hip).
+// Pieces shared by the time-major LSTM kernels (lstm_tm_fwd.hip, lstm_tm_bwd.hip, lstm_grads_jobs.hip,
+// lstm_chain.hip, time4_head.hip): tile constants, streamers, the fused pool, and the host side's shape
+// predicates with the dispatcher that turns a launch's run-time shape into template arguments.
 #pragma once
 #include "common.h"
 
+#include <cstdlib>
 #include <type_traits>
+#include <utility>
+
+#ifndef TM_RG_BF16H
+#define TM_RG_BF16H 1    // recompute-gates pairs save layer A's h in bf16 (its only readers stage it as bf16; A/B: 0)
+#endif
+#ifndef TM_RG_BF16C
+#define TM_RG_BF16C 1    // recompute-gates layers save c_t in bf16 (the forward keeps fp32 in registers; A/B: 0)
+#endif
 
 namespace gq {
+
+// ---- host: a run-time value as a compile-time constant. f is a generic lambda called with
+// std::integral_constant<int, V> (read it as decltype(v)::value); a value outside Vs... raises `what`.
+template <int... Vs, class F>
+void dispatch_int(int v, const char* what, F&& f) {
+  const bool hit = ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  TORCH_CHECK(hit, what);
+}
+template <class F>
+void dispatch_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+// several flags at once: f(c0, c1, ...) with std::true_type / std::false_type
+template <class F>
+void dispatch_bools(F&& f) { f(); }
+template <class F, class... Bs>
+void dispatch_bools(F&& f, bool b, Bs... bs) {
+  dispatch_bool(b, [&](auto c) { dispatch_bools([&](auto... cs) { f(c, cs...); }, bs...); });
+}
+
+// ---- host: what the time-major kernels take. The TORCH_CHECKs of the entry points and the pruning of
+// template instances (tm_combo_ok) are these same functions, so the two cannot drift apart.
+inline int tm_granule(int Din, const void* x) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x);
+  if (Din % 4 == 0 && a % 16 == 0) return 4;
+  if (Din % 2 == 0 && a % 8 == 0) return 2;
+  return 1;
+}
+
+// H in {16, 32, 64}: one cell per lane, H / 4 waves. Larger hidden sizes keep the seq-major kernels of
+// lstm.hip / lstm_grads.hip. The per-step x tile must fit the loader lanes and Din + 1 (bias row) must fit 128.
+constexpr bool tm_supported(int H, int Din, int gr) {
+  if (H != 16 && H != 32 && H != 64) return false;
+  if (Din < 1 || Din > 127) return false;
+  return 16 * Din / gr <= 16 * H;
+}
+
+// x channel blocks of 32 (KX); 3 runs as 4
+constexpr int tm_kx(int Din) { return (Din + 31) / 32 <= 2 ? (Din + 31) / 32 : 4; }
+
+// recompute-gates backward (lstm_tm_bwd_body RG): one cell per lane with the x / h streams of the
+// fused weight-gradient kernel (H <= 32, 16-byte x granules)
+constexpr bool tm_rg_ok(int H, int gr) { return (H == 16 || H == 32) && gr == 4; }
+
+// some Din has KX channel blocks and passes tm_supported(H, Din, GR): only those (H, KX, GR) are instantiated
+template <int H, int KX, int GR>
+constexpr bool tm_combo_ok() {
+  for (int Din = 1; Din <= 127; ++Din)
+    if (tm_kx(Din) == KX && tm_supported(H, Din, GR)) return true;
+  return false;
+}
+
+// (H, KX, GR) of a launch as constants: f(h, kx, gr). A triple no supported Din reaches ends in an error.
+template <int... Hs, class F>
+void tm_dispatch(int H, int Din, int gr, const char* what, F&& f) {
+  dispatch_int<Hs...>(H, what, [&](auto h) {
+    dispatch_int<1, 2, 4>(tm_kx(Din), "lstm_tm: x channel blocks", [&](auto kx) {
+      dispatch_int<1, 2, 4>(gr, "lstm_tm: x granule", [&](auto g) {
+        if constexpr (tm_combo_ok<decltype(h)::value, decltype(kx)::value, decltype(g)::value>()) f(h, kx, g);
+        else TORCH_CHECK(false, "lstm_tm: no instance for (H, Din, granule) = (", H, ", ", Din, ", ", gr, ")");
+      });
+    });
+  });
+}
+
+// GNNQC_TM_RECDX=0: multi-column-block layers take dx from weight-gradient slabs + their sum
+// (the earlier layout) instead of from the recurrence
+inline bool tm_rec_dx() {       // read per call (host side of a launch; tests toggle it)
+  const char* e = std::getenv("GNNQC_TM_RECDX");
+  return !(e != nullptr && e[0] == '0');
+}
+
+// Weight gradients inside the backward recurrence (lstm_tm_bwd_wg_kernel) for layers of at least
+// GNNQC_TM_FUSED_WGRAD_MIN_TILES 16-sequence tiles (default 64: with few tiles the separate pass
+// spreads the rows over the whole GPU, the recurrence's workgroups cannot); GNNQC_TM_FUSED_WGRAD=0
+// turns it off. Read per call (tests switch them).
+inline bool tm_fused_wgrad(int H, int Din, int gr, int ntiles) {
+  const char* e = std::getenv("GNNQC_TM_FUSED_WGRAD");
+  if (e != nullptr && e[0] == '0') return false;
+  const char* m = std::getenv("GNNQC_TM_FUSED_WGRAD_MIN_TILES");
+  const int min_tiles = m != nullptr ? std::atoi(m) : 64;
+  return tm_rg_ok(H, gr) && Din <= 64 && ntiles >= min_tiles;
+}
 
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 

@@ -183,7 +183,6 @@ void peer_ipc_close(int64_t ptr) { (void)hipIpcCloseMemHandle(reinterpret_cast<v
 
 // g (float32, contiguous, n <= cap): replaced by scale * (sum over ranks); bases: every rank's
 // region address in this process (own region at [rank]); ctl = region tail (own)
-int* chain_ctl(int dev);   // lstm_chain.hip: the device's chain control words
 
 void peer_allreduce(at::Tensor g, at::IntArrayRef bases, at::Tensor region, int64_t rank, int64_t cap,
                     double scale) {

@@ -7,7 +7,7 @@
 #include "common.h"
 
 namespace gq {
-bool lstm_defer_reduce(bool flag);      // lstm_tm.hip
+bool lstm_defer_reduce(bool flag);      // lstm_grads_jobs.hip
 int64_t lstm_reduce_flush();
 // returns the previous value (see deterministic_mode in common.h)
 static bool set_deterministic(bool flag) {
@@ -27,7 +27,7 @@ TORCH_LIBRARY(gnnqc, m) {
   m.def("lstm_bwd(Tensor dh, Tensor gates, Tensor cseq, Tensor U, bool bf16) -> Tensor");
   m.def("lstm_grads(Tensor dz, Tensor x, Tensor hseq, Tensor W, Tensor(a!) dW, Tensor(b!) dU, Tensor(c!) db, "
         "bool need_dx) -> Tensor");
-  // time-major LSTM with fused backward (lstm_tm.hip)
+  // time-major LSTM (lstm_tm_fwd.hip, lstm_tm_bwd.hip) and its weight-gradient jobs (lstm_grads_jobs.hip)
   m.def("lstm_tm_fwd(Tensor x, Tensor W, Tensor U, Tensor b, bool train, bool store_gates=True) -> Tensor[]");
   m.def("lstm_tm2_fwd(Tensor x, Tensor WA, Tensor UA, Tensor bA, Tensor WB, Tensor UB, Tensor bB, "
         "bool train, bool store_gates=True, int pool=0) -> Tensor[]");

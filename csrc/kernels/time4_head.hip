@@ -15,7 +15,7 @@
 // and every spill reload drained the vector-memory counter. At 8 waves a wave holds 256.
 //   forward   lane = 4 cells (unit 4(w + 8cc) + quad of sequence col); the MFMA A rows are
 //             permuted so a 16x16 tile delivers the i, f, g, o pre-activations of the lane's own
-//             cell (as lstm_tm.hip). The whole input sequence of the tile is staged in LDS once.
+//             cell (as lstm_tm_fwd.hip). The whole input sequence of the tile is staged in LDS once.
 //   backward  dh_rec^T = U dz^T: wave w owns unit tile w over the full K = 4H (16 MFMAs, U
 //             fragments resident); dx^T = W dz^T: din tile w % 4 over gate-column half w / 4.
 //             The forward state (gates, c) streams through a 2-deep register ring.
@@ -25,7 +25,6 @@
 
 namespace gq {
 
-int* chain_ctl(int dev);     // lstm_chain.hip: per-device control words ([4] / [5]: head tickets)
 
 constexpr int T4H = 128;                 // hidden size
 constexpr int T4G = 4 * T4H;             // gate columns

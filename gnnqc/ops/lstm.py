@@ -93,7 +93,7 @@ class _Pipe:
 PIPE_MAX_SEQ = 2048
 
 
-_MULTI_MAX = 12        # jobs per lstm_grads_multi launch (lstm_tm.hip MULTI_MAX)
+_MULTI_MAX = 12        # jobs per lstm_grads_multi launch (lstm_grads_jobs.hip MULTI_MAX)
 
 
 def _pipe_on(sinks, n_seq: int) -> bool:
@@ -655,7 +655,7 @@ def check_chain(device, rejected_before: Optional[int] = None) -> int:
 
 
 class _HipLSTMTM(torch.autograd.Function):
-    """Time-major LSTM layer (``lstm_tm.hip``): x [T, Mp, Din] -> h [T, Mp, H] (or the last
+    """Time-major LSTM layer (``lstm_tm_fwd.hip`` / ``lstm_tm_bwd.hip``): x [T, Mp, Din] -> h [T, Mp, H] (or the last
     step [Mp, H]). The backward is ONE fused kernel: recurrence, dx, and dW/dU/db
     accumulated straight into the gradient buffers (direct mode) or returned."""
 
@@ -803,7 +803,7 @@ def lstm_pair_tm(x_tm, A, B, pool: int = 0) -> torch.Tensor:
 
 def recompute_gates(x: torch.Tensor, H: int, weight_grads: bool) -> bool:
     """Whether a time-major layer's forward saves no gates and its backward recomputes them from
-    x_t and h_{t-1} (``lstm_tm.hip`` RG: bitwise the forward's pre-activations; halves the forward's
+    x_t and h_{t-1} (``lstm_tm_bwd_body.h`` RG: bitwise the forward's pre-activations; halves the forward's
     state stream). H in {16, 32}, 16-byte x granules, and the backward must take the fused kernel:
     frozen weights (integrated gradients), or too many sequences for the pipelined backward
     (``PIPE_MAX_SEQ``). ``GNNQC_TM_RG=0`` keeps the saved gates."""

@@ -1,6 +1,6 @@
 """Reference LSTM with the HIP kernels' rounding points, for numerics tests.
 
-The recurrences run on bf16 MFMA (``lstm_chain.hip``, ``lstm_tm.hip``, ``time4_head.hip``,
+The recurrences run on bf16 MFMA (``lstm_chain.hip``, ``lstm_tm_fwd.hip`` / ``lstm_tm_bwd.hip``, ``time4_head.hip``,
 ``lstm_grads.hip``), so comparing them with a plain float64 model needs tolerances of several
 percent (bf16 has 8 significand bits), loose enough to hide a real bug. This reference keeps
 float64 arithmetic everywhere EXCEPT where the kernels round, and rounds there exactly like
@@ -11,7 +11,7 @@ forward   z_t = bf16(x_t) bf16(W) + bf16(h_{t-1}) bf16(U) + b; gates / c / h in 
           them, ``lstm_tm_common.h gates_pack``) and full precision for H = 128 (the training
           chain's time4; the standalone time4 layer and lstm_fwd<128> save bf16 gates as well -
           a difference well inside the tests' tolerances);
-          ``saved="rg"`` models the recompute-gates layers instead (lstm_tm.hip RG): their backward
+          ``saved="rg"`` models the recompute-gates layers instead (lstm_tm_bwd_body.h RG): their backward
           recomputes the gates in fp32 from the same bf16 operands (no gate rounding) and reads c_t
           and c_{t-1} back from bf16 (TM_RG_BF16C), so tanh(c_t) and c_{t-1} come from bf16(c). A
           pair's layer-A h saved in bf16 (TM_RG_BF16H) needs no modelling: its only readers take h

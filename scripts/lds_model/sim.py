@@ -1,6 +1,6 @@
 """LDS bank-conflict model of gfx950 (MI355X_MICROARCH.md §LDS): per instruction kind, the lane groups
 serviced per LDS cycle and the bank function; cycles() = sum over groups of the worst bank's distinct dwords.
-Used to choose the LDS pitches of lstm_tm.hip's backward (bwd.py / search.py) and to price the WG images
+Used to choose the LDS pitches of the time-major backward (lstm_tm_bwd_body.h) (bwd.py / search.py) and to price the WG images
 (wg.py). Run: python scripts/lds_model/search.py"""
 # LDS bank-conflict model from MI355X_MICROARCH.md §LDS
 import itertools

@@ -393,7 +393,7 @@ def test_lstm_time_major_fused_bwd_matches_eager(cuda_device, H, Din, ret_seq, w
 @pytest.mark.parametrize("wgrad", [True, False])
 @pytest.mark.parametrize("pair", [False, True])
 def test_lstm_tm_recomputed_gates_match_saved_gates(cuda_device, monkeypatch, H, Din, wgrad, pair):
-    """Recompute-gates backward (lstm_tm.hip RG: the forward saves only c, the backward recomputes
+    """Recompute-gates backward (lstm_tm_bwd_body.h RG: the forward saves only c, the backward recomputes
     i, f, g, o from x_t and h_{t-1}) vs the saved-gates form: identical forward output, gradients
     within bf16-gate rounding of each other, and the RG gradients against an fp64 eager oracle.
     (Sharp bounds against the rounding-aware oracle, per branch: tests/test_lstm_tm_kernels_gpu.py.)"""

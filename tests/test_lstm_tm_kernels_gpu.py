@@ -1,5 +1,5 @@
-"""Time-major LSTM kernels (``csrc/kernels/lstm_tm.hip``: ``lstm_tm_fwd``, ``lstm_tm2_fwd`` and
-``lstm_tm_bwd``) called directly through ``hip_ops()``, over their template instances, ring
+"""Time-major LSTM kernels (``csrc/kernels/lstm_tm_fwd.hip``: ``lstm_tm_fwd``, ``lstm_tm2_fwd``;
+``csrc/kernels/lstm_tm_bwd.hip``: ``lstm_tm_bwd``) called directly through ``hip_ops()``, over their template instances, ring
 prologues, granules, weight-gradient paths, record reduction, un-pooling and the layer pair, against
 the rounding-aware float64 oracle :class:`gnnqc.ops.lstm_ref.KernelLSTM` on the CPU
 (``rounding=True``; ``saved="rg"`` where the backward recomputes its gates; two stacked layers for

@@ -11,17 +11,17 @@ import test_lstm_tm_kernels_gpu as S
 
 _IDS = [c.name for c in S.TM_CASES]
 
-# ------------------------------------------------------------------ constants of lstm_tm.hip, mirrored
-K_H = (16, 32, 64)              # GQ_TM_H_DISPATCH
-K_H_PAIR = (16, 32)             # GQ_TM2_H_DISPATCH, tm_rg_ok, tm_fused_wgrad
+# ------------------------------------------------------------------ constants of lstm_tm_fwd.hip / lstm_tm_bwd.hip, mirrored
+K_H = (16, 32, 64)              # tm_supported
+K_H_PAIR = (16, 32)             # lstm_tm2_fwd, tm_rg_ok, tm_fused_wgrad
 K_DIN_MAX = 127                 # tm_supported
 K_FUSED_DIN_MAX = 64            # tm_fused_wgrad, the recompute-gates backward
 K_MIN_TILES_DEFAULT = 64        # GNNQC_TM_FUSED_WGRAD_MIN_TILES
 K_GR_CB = 64                    # lstm_grads: gate columns per column block
 K_GROUP_SPLITS = 512            # split records per reduction group
-K_FWD_D = 6                     # tm_fwd_cfg / lstm_tm2_fwd ring depth
-K_BWD_D, K_BWD_D_H64 = 4, 2     # tm_bwd_cfg
-K_RG_D = 4                      # frozen recompute-gates backward
+K_FWD_D = 6                     # TM_FWD_D: lstm_tm_fwd / lstm_tm2_fwd ring depth
+K_BWD_D, K_BWD_D_H64 = 4, 2     # tm_bwd_depth
+K_RG_D = 4                      # TM_RG_D: frozen recompute-gates backward
 K_TMW_D16, K_TMW_D32 = 4, 6     # lstm_tm_bwd_wg_kernel
 K_ELEMS_SECOND_REFERENCE = 200000       # Mp T (Din + 4 H): cases above it skip the autograd route
 
