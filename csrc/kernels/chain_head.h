@@ -11,9 +11,14 @@
 //             sums the per-tile partials in tile order (deterministic) into the loss and the
 //             metric accumulators.
 //   backward: recomputes the head forward of its 16 rows, back-propagates dloss, leaves
-//             dh_{T-1} of time4 in LDS and writes the tile's weight-gradient record; the
-//             workgroup holding the last ticket sums the records in tile order and adds them to
-//             the gradients.
+//             dh_{T-1} of time4 in LDS and writes the tile's weight-gradient record; once every
+//             tile's record is in, each workgroup sums its slice of the records in tile order and
+//             adds it to the gradients.
+//   hand-over (the chain's training step): the forward launch's head goes on from its own z1, a1,
+//             z2 and logit to dh_{T-1} for dL/dloss = 1 (chain_head_dh: one head forward, no records
+//             on the forward's tail) and hands it to the backward launch, whose reverse recurrence
+//             starts from it at once; that launch runs the backward above AFTER its time4 steps, for
+//             the records alone, in workgroups that would otherwise idle until the chain is done.
 // 512 threads (8 waves); a thread owns unit j = tid & 63 of rows w = tid >> 6 and w + 8. The
 // backward also runs in 1024-thread workgroups (the chain backward launch): there tid is taken
 // modulo 512, so waves 8..15 repeat waves 0..7's work - the same values to the same LDS / global
@@ -74,19 +79,28 @@ __device__ __forceinline__ float ch_ld(const float* p) {
 __device__ __forceinline__ float ch_leaky(float z, float a) { return z > 0.f ? z : a * z; }
 __device__ __forceinline__ float ch_dleaky(float z, float a) { return z > 0.f ? 1.f : a; }
 
-// Sum of mask[0..M) over the workgroup (red: CH_NW floats of LDS). Contains a barrier.
 __device__ __forceinline__ int ch_tid() { return threadIdx.x & (64 * CH_NW - 1); }
 
-__device__ __forceinline__ float ch_mask_sum(const float* __restrict__ mask, int M, float* red) {
+// Sum of mask[0..M) over the workgroup in two halves: the per-wave partial sums -> red (CH_NW floats
+// of LDS), then, after a barrier, their total. (The forward launch issues the first half while its
+// time4 stage still waits for input and reads the total after the last step.)
+__device__ __forceinline__ void ch_mask_partials(const float* __restrict__ mask, int M, float* red) {
   float s = 0.f;
   for (int i = ch_tid(); i < M; i += 64 * CH_NW) s += ch_ld(mask + i);   // (agent scope: the labels may come from this launch's producers)
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[ch_tid() >> 6] = s;
-  __syncthreads();
+}
+__device__ __forceinline__ float ch_mask_total(const float* red) {
   float t = 0.f;
 #pragma unroll
   for (int k = 0; k < CH_NW; ++k) t += red[k];
   return t;
+}
+// Both halves at once. Contains a barrier.
+__device__ __forceinline__ float ch_mask_sum(const float* __restrict__ mask, int M, float* red) {
+  ch_mask_partials(mask, M, red);
+  __syncthreads();
+  return ch_mask_total(red);
 }
 
 // D^T tile (16 outputs x 16 rows) of out[r][o] = sum_k act[r][k] * Wt[k][o], o in [16 ot, +16),
@@ -200,9 +214,15 @@ template <int F>
 __device__ __forceinline__ void chain_head_fwd_handoff(const ChainHead hd, int tile, int ntiles, char* scratch);
 // handoff = false: stop before the tile's loss partials are handed off (the caller runs
 // chain_head_fwd_handoff later, e.g. after more work whose latency hides the stores' acknowledgements)
+// keep / sz1: what chain_head_dh continues from - this thread's z2, logit, label and mask of its two
+// rows (registers) and z1 of the tile ([16][CH_AP], LDS; a1 stays in the forward's scratch anyway)
+struct ChainHeadKeep {
+  float z2[2], z[2], yy[2], mm[2];
+};
 template <int F>
 __device__ __forceinline__ void chain_head_fwd(const ChainHead hd, int tile, int ntiles, const float* hl, char* scratch,
-                                               bool staged = false, bool handoff = true) {
+                                               bool staged = false, bool handoff = true, float* sz1 = nullptr,
+                                               ChainHeadKeep* keep = nullptr) {
   float* part = reinterpret_cast<float*>(scratch);    // [2][16][CH_AP]
   float* sa1 = part + 2 * 16 * CH_AP;                 // [16][CH_AP]
   float* rowv = sa1 + 16 * CH_AP;                     // [16][8]
@@ -219,11 +239,17 @@ __device__ __forceinline__ void chain_head_fwd(const ChainHead hd, int tile, int
     mm[q] = ch_ld(hd.mask + rc);
   }
   float z2[2];
-  ch_head_z2<F>(hd, sW1, sW2, hl, part, nullptr, sa1, z2);
+  ch_head_z2<F>(hd, sW1, sW2, hl, part, sz1, sa1, z2);
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int r = w + 8 * q, row = tile * 16 + r;
     const float z = wave_sum(ch_leaky(z2[q], hd.alpha2) * w3j) + b3;
+    if (keep != nullptr) {
+      keep->z2[q] = z2[q];
+      keep->z[q] = z;
+      keep->yy[q] = yy[q];
+      keep->mm[q] = mm[q];
+    }
     if (j == 0) {
       const bool valid = row < hd.M;
       const float m = valid ? mm[q] : 0.f, y = yy[q];
@@ -280,72 +306,25 @@ __device__ __forceinline__ void chain_head_fwd_handoff(const ChainHead hd, int t
   }
 }
 
-// LDS bytes of the backward prologue scratch (dh_{T-1} output tile excluded)
-template <int F>
-struct ChainHeadBwdLds {
-  static constexpr int BYTES = (16 * (F + 4) + 2 * 16 * CH_AP + 5 * 16 * CH_AP + 32 + (F + CH_HU) * CH_WP) * 4;
-};
+// dL/dz of one row: gl = dL/dloss, n = the mask sum over the M rows
+__device__ __forceinline__ float ch_head_d(const ChainHead& hd, bool valid, float gl, float n, float z, float y, float m) {
+  const float wc = y > 0.5f ? hd.w1 : hd.w0;
+  return valid ? gl / fmaxf(n, 1.f) * m * wc * (sigmoidf_fast(z) - y) : 0.f;
+}
 
-// Backward of the head for the 16 rows of `tile`, whose time4 output hT ([16][F] rows of the
-// tile, global) feeds it: dh_{T-1} -> dh [16][F + 4] (LDS), the tile's weight-gradient record ->
-// hd.gpart[tile], then the tile's arrival is counted in hd.ticket (chain_head_bwd_reduce waits
-// for all of them).
-// Precompute mode (the chain FORWARD's time4 stage, right after the head forward; everything here
-// is linear in dL/dloss): hld >= 0 reads hT as the [16][hld] LDS tile of h_{T-1}, unit_gl takes
-// dL/dloss = 1 (the backward scales dh and the reduced records by the real one), count = false
-// leaves the arrival ticket alone (the records are complete at the launch boundary), and nlive
-// is the number of live waves that share the record tiles.
+// From dL/dz (d) of this thread's two rows to the gradient of the head's input:
+// dz2 = d W3^T leaky'(z2) -> sz2, da1 = dz2 W2^T, dz1 = da1 leaky'(z1) -> sdz1, dh = dz1 W1^T -> dh
+// [16][F + 4] (LDS; no barrier after its stores). part [2][16][CH_AP], sz1 (z1 of the tile) and the
+// weight images are the head forward's; the caller's LDS writes before the call are published by
+// the first barrier here.
 template <int F>
-__device__ __forceinline__ void chain_head_bwd(const ChainHead hd, const float* __restrict__ hT, int tile, int ntiles,
-                                               float* dh, char* scratch, int hld = -1, bool unit_gl = false,
-                                               bool count = true, int nlive = 0, const float* pW1 = nullptr,
-                                               const float* pW2 = nullptr) {
+__device__ __forceinline__ void ch_head_dh(const ChainHead& hd, const float d[2], const float z2[2], float w3j,
+                                           const float* sW1, const float* sW2, float* part, const float* sz1,
+                                           float* sz2, float* sdz1, float* dh) {
   constexpr int HLP = F + 4, PT = 16 * CH_AP;
-  using Rec = ChainHeadRec<F>;
-  float* sh = reinterpret_cast<float*>(scratch);     // [16][HLP]
-  float* part = sh + 16 * HLP;                       // [2][16][CH_AP]
-  float* sz1 = part + 2 * PT;                        // [16][CH_AP] z1
-  float* sa1 = sz1 + PT;                             // [16][CH_AP] leaky(z1)
-  float* sz2 = sa1 + PT;                             // [16][CH_AP] dz2
-  float* sad = sz2 + PT;                             // [16][CH_AP] leaky(z2) * d
-  float* sdz1 = sad + PT;                            // [16][CH_AP] dz1
-  float* misc = sdz1 + PT;                           // [32]: d per row, mask-sum reduction
-  // (pW1 / pW2: images already staged by the caller, e.g. the forward's head)
-  float* sW1 = pW1 != nullptr ? const_cast<float*>(pW1) : misc + 32;   // [F][CH_WP]
-  float* sW2 = pW2 != nullptr ? const_cast<float*>(pW2) : sW1 + F * CH_WP;   // [64][CH_WP]
-  if (pW1 == nullptr) ch_stage_weights<F>(hd, sW1, sW2);
   const int tid = ch_tid(), w = tid >> 6, j = tid & 63;
-  const int l = tid & 63, lm = l & 15, lq = l >> 4;
-  const int row0 = tile * 16;
-  const float* hsrc = hld < 0 ? hT + (size_t)row0 * F : hT;
-  const int hp = hld < 0 ? F : hld;
-  for (int e = tid; e < 16 * F / 4; e += 64 * CH_NW) {
-    const int rr = 4 * e / F, k = 4 * e % F;
-    const float4 v = *reinterpret_cast<const float4*>(hsrc + (size_t)rr * hp + k);
-    *reinterpret_cast<float4*>(sh + rr * HLP + k) = v;
-  }
-  const float w3j = hd.W3[j], b3 = hd.b3[0], gl = unit_gl ? 1.f : hd.dloss[0];
-  float yy[2], mm[2];
 #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int rc = min(row0 + w + 8 * q, hd.M - 1);
-    yy[q] = ch_ld(hd.y + rc);
-    mm[q] = ch_ld(hd.mask + rc);
-  }
-  const float n = ch_mask_sum(hd.mask, hd.M, misc + 16);    // (its barrier also publishes sh)
-  float z2[2];
-  ch_head_z2<F>(hd, sW1, sW2, sh, part, sz1, sa1, z2);
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int r = w + 8 * q;
-    const float a2 = ch_leaky(z2[q], hd.alpha2);
-    const float z = wave_sum(a2 * w3j) + b3;
-    const float wc = yy[q] > 0.5f ? hd.w1 : hd.w0;
-    const float d = (row0 + r < hd.M) ? gl / fmaxf(n, 1.f) * mm[q] * wc * (sigmoidf_fast(z) - yy[q]) : 0.f;
-    sz2[r * CH_AP + j] = d * w3j * ch_dleaky(z2[q], hd.alpha2);
-    sad[r * CH_AP + j] = a2 * d;
-    if (j == 0) misc[r] = d;
-  }
+  for (int q = 0; q < 2; ++q) sz2[(w + 8 * q) * CH_AP + j] = d[q] * w3j * ch_dleaky(z2[q], hd.alpha2);
   __syncthreads();
   {   // da1 = dz2 W2^T (A = W2 rows), dz1 = da1 * leaky'(z1)
     const int ot = w & 3, kh = w >> 2;
@@ -365,6 +344,101 @@ __device__ __forceinline__ void chain_head_bwd(const ChainHead hd, const float* 
     const int ot = w + CH_NW * q;
     ch_put(dh, HLP, ot, ch_mm_wt<16>(sW1, CH_WP, ot, 0, sdz1, CH_AP));
   }
+}
+
+// LDS bytes that chain_head_dh needs beyond the head forward's scratch (dh output tile excluded):
+// z1, dz2, dz1; the mask's partial sums (ch_mask_partials) wait in the first floats of dz1
+template <int F>
+struct ChainHeadDhLds {
+  static constexpr int BYTES = 3 * 16 * CH_AP * 4;
+};
+template <int F>
+__device__ __forceinline__ float* ch_head_dh_sz1(char* dhscratch) { return reinterpret_cast<float*>(dhscratch); }
+template <int F>
+__device__ __forceinline__ float* ch_head_dh_red(char* dhscratch) {
+  return reinterpret_cast<float*>(dhscratch) + 2 * 16 * CH_AP;
+}
+
+// The training forward's continuation of chain_head_fwd (same 512 threads, same rows, called with
+// sz1 = ch_head_dh_sz1(dhscratch) and `keep`): dh_{T-1} for dL/dloss = 1 -> dh [16][F + 4] (LDS) from
+// what the forward left - z1 and a1 in LDS, z2, the logit, label and mask in registers - so the head
+// forward runs once. The arithmetic is chain_head_bwd's, in its order: dh is bit for bit what that
+// computes with dL/dloss = 1. The backward launch scales it by the real dL/dloss and builds the
+// weight-gradient records itself (chain_head_bwd after its reverse steps, where it has time).
+template <int F>
+__device__ __forceinline__ void chain_head_dh(const ChainHead hd, int tile, const ChainHeadKeep& keep, char* fscratch,
+                                              char* dhscratch, float* dh) {
+  float* part = reinterpret_cast<float*>(fscratch);             // the forward's [2][16][CH_AP]
+  const float* sW1 = ch_head_fwd_weights<F>(fscratch);
+  const float* sW2 = sW1 + F * CH_WP;
+  float* sz1 = ch_head_dh_sz1<F>(dhscratch);
+  float* sz2 = sz1 + 16 * CH_AP;
+  float* sdz1 = sz2 + 16 * CH_AP;
+  const int tid = ch_tid(), w = tid >> 6, j = tid & 63;
+  const float w3j = hd.W3[j];
+  const float n = ch_mask_total(ch_head_dh_red<F>(dhscratch));   // (overwritten two barriers later)
+  float d[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    d[q] = ch_head_d(hd, tile * 16 + w + 8 * q < hd.M, 1.f, n, keep.z[q], keep.yy[q], keep.mm[q]);
+  ch_head_dh<F>(hd, d, keep.z2, w3j, sW1, sW2, part, sz1, sz2, sdz1, dh);
+}
+
+// LDS bytes of the backward prologue scratch (dh_{T-1} output tile excluded)
+template <int F>
+struct ChainHeadBwdLds {
+  static constexpr int BYTES = (16 * (F + 4) + 2 * 16 * CH_AP + 5 * 16 * CH_AP + 32 + (F + CH_HU) * CH_WP) * 4;
+};
+
+// Backward of the head for the 16 rows of `tile`, whose time4 output hT ([16][F] rows of the
+// tile, global) feeds it: recomputes the head forward, dh_{T-1} -> dh [16][F + 4] (LDS), the tile's
+// weight-gradient record -> hd.gpart[tile] (its tiles shared by all waves of the workgroup), then
+// the tile's arrival is counted in hd.ticket (chain_head_bwd_reduce waits for all of them).
+template <int F>
+__device__ __forceinline__ void chain_head_bwd(const ChainHead hd, const float* __restrict__ hT, int tile, int ntiles,
+                                               float* dh, char* scratch) {
+  constexpr int HLP = F + 4, PT = 16 * CH_AP;
+  using Rec = ChainHeadRec<F>;
+  float* sh = reinterpret_cast<float*>(scratch);     // [16][HLP]
+  float* part = sh + 16 * HLP;                       // [2][16][CH_AP]
+  float* sz1 = part + 2 * PT;                        // [16][CH_AP] z1
+  float* sa1 = sz1 + PT;                             // [16][CH_AP] leaky(z1)
+  float* sz2 = sa1 + PT;                             // [16][CH_AP] dz2
+  float* sad = sz2 + PT;                             // [16][CH_AP] leaky(z2) * d
+  float* sdz1 = sad + PT;                            // [16][CH_AP] dz1
+  float* misc = sdz1 + PT;                           // [32]: d per row, mask-sum reduction
+  float* sW1 = misc + 32;                            // [F][CH_WP]
+  float* sW2 = sW1 + F * CH_WP;                      // [64][CH_WP]
+  ch_stage_weights<F>(hd, sW1, sW2);
+  const int tid = ch_tid(), w = tid >> 6, j = tid & 63;
+  const int l = tid & 63, lm = l & 15, lq = l >> 4;
+  const int row0 = tile * 16;
+  for (int e = tid; e < 16 * F / 4; e += 64 * CH_NW) {
+    const int rr = 4 * e / F, k = 4 * e % F;
+    const float4 v = *reinterpret_cast<const float4*>(hT + (size_t)(row0 + rr) * F + k);
+    *reinterpret_cast<float4*>(sh + rr * HLP + k) = v;
+  }
+  const float w3j = hd.W3[j], b3 = hd.b3[0], gl = hd.dloss[0];
+  float yy[2], mm[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int rc = min(row0 + w + 8 * q, hd.M - 1);
+    yy[q] = ch_ld(hd.y + rc);
+    mm[q] = ch_ld(hd.mask + rc);
+  }
+  const float n = ch_mask_sum(hd.mask, hd.M, misc + 16);    // (its barrier also publishes sh)
+  float z2[2], d[2];
+  ch_head_z2<F>(hd, sW1, sW2, sh, part, sz1, sa1, z2);
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = w + 8 * q;
+    const float a2 = ch_leaky(z2[q], hd.alpha2);
+    const float z = wave_sum(a2 * w3j) + b3;
+    d[q] = ch_head_d(hd, row0 + r < hd.M, gl, n, z, yy[q], mm[q]);
+    sad[r * CH_AP + j] = a2 * d[q];
+    if (j == 0) misc[r] = d[q];
+  }
+  ch_head_dh<F>(hd, d, z2, w3j, sW1, sW2, part, sz1, sz2, sdz1, dh);
   // weight gradients over the tile's 16 rows (K = rows): A[m][kk] = act1[4s + kk][16 it + m],
   // B[kk][n] = act2[4s + kk][16 jt + n]
   auto wgrad = [&](const float* a1, int lda1, int it, const float* a2, int jt) {
@@ -378,7 +452,7 @@ __device__ __forceinline__ void chain_head_bwd(const ChainHead hd, const float* 
   float* rec = hd.gpart + (size_t)tile * Rec::PITCH;
   float* rec2 = rec + F * CH_HU + CH_HU;
   // the record tiles are spread over ALL waves of the workgroup (8 or 16), each stored once
-  const int wa = threadIdx.x >> 6, nwa = nlive > 0 ? nlive : (int)(blockDim.x >> 6);
+  const int wa = threadIdx.x >> 6, nwa = (int)(blockDim.x >> 6);
   for (int t = wa; t < F / 16 * 4; t += nwa) {        // dW1 [F][64]: (F/16) x 4 tiles
     const int it = t >> 2, jt = t & 3;
     const ch_f4 acc = wgrad(sh, HLP, it, sdz1, jt);
@@ -408,10 +482,6 @@ __device__ __forceinline__ void chain_head_bwd(const ChainHead hd, const float* 
     for (int rr = 0; rr < 16; ++rr) s += misc[rr];
     ch_st(rec2 + CH_HU * CH_HU + 2 * CH_HU, s);                 // db3
   }
-  if (!count) {
-    __syncthreads();
-    return;
-  }
   // (sc1 stores, every wave's vmcnt(0), barrier, one lane's counter add: no fence)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -423,15 +493,11 @@ __device__ __forceinline__ void chain_head_bwd(const ChainHead hd, const float* 
 // sums its 1/ntiles slice of the records over the tiles in tile order (deterministic) and adds
 // it to the gradients; the last one to finish re-arms both counters. One workgroup reducing all
 // of it took ~60 us (25 rounds of 8 dependent-latency loads per thread).
-// pre: the records come from an earlier launch (chain_head_bwd's precompute mode): no arrival wait,
-// and every sum is scaled by `scale` (dL/dloss).
 template <int F>
-__device__ __forceinline__ void chain_head_bwd_reduce(const ChainHead hd, int tile, int ntiles, bool pre = false,
-                                                      float scale = 1.f) {
+__device__ __forceinline__ void chain_head_bwd_reduce(const ChainHead hd, int tile, int ntiles) {
   using Rec = ChainHeadRec<F>;
   __shared__ int bad;
-  if (threadIdx.x == 0 && pre) bad = 0;
-  if (threadIdx.x == 0 && !pre) {
+  if (threadIdx.x == 0) {
     int nap = 1, it = 0;
     bad = 0;
     while (__hip_atomic_load(hd.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ntiles) {
@@ -464,7 +530,7 @@ __device__ __forceinline__ void chain_head_bwd_reduce(const ChainHead hd, int ti
       for (int q = 0; q < RB; ++q) {
       const int e = e0 + q * (int)blockDim.x;
       if (e >= e1) break;
-      const float s = acc[q] * scale;
+      const float s = acc[q];
       // (adam_flagged decides the step from such flags instead of scanning the gradient buffer)
       if (!isfinite(s)) __hip_atomic_store(hd.ctl + 7, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       int o = e;

@@ -115,8 +115,8 @@ struct ChainT4 {
   unsigned char* pin_idx;            //   and its argmax bytes
   int T, Din, Dw, on;
   ChainHead hd;
-  float* hb;                         // train: the head backward precomputed here ([ntiles][16][128]
-                                     // dh_{T-1} | records, dL/dloss = 1; nullptr: the backward runs it)
+  float* hb;                         // train: dh_{T-1} of the head for dL/dloss = 1, computed here
+                                     // ([ntiles][16][128]; nullptr: the backward launch runs the head backward first)
 };
 
 struct ChainArgs {
@@ -716,10 +716,10 @@ struct ChainT4Lds {
   static constexpr int HS = 2 * 16 * (128 + 8) * 2;       // bf16 h_{t-1} (double buffer)
   static constexpr int XS = 2 * 16 * (64 + 8) * 2;        // bf16 x_t (double buffer)
   static constexpr int HL = 16 * (128 + 4) * 4;           // fp32 h_{T-1} for the head
-  static constexpr int DHT = 16 * (128 + 4) * 4;          // precomputed head backward: dh_{T-1}
-  // (the head backward's dh tile and scratch follow the head forward's, whose weight images it reuses)
+  static constexpr int DHT = 16 * (128 + 4) * 4;          // dh_{T-1} of the head (chain_head_dh)
+  // (chain_head_dh's dh tile and scratch follow the head forward's, whose tiles and weight images it reuses)
   static constexpr int HF = ChainHeadFwdLds<128>::BYTES;
-  static constexpr int HB = DHT + ChainHeadBwdLds<128>::BYTES - (128 + CH_HU) * CH_WP * 4;   // (no weight images)
+  static constexpr int HB = DHT + ChainHeadDhLds<128>::BYTES;
   static constexpr int BYTES = HS + XS + HL + HF + HB;
 };
 
@@ -911,26 +911,31 @@ __global__ __launch_bounds__(1024) void lstm_chain_fwd_kernel(ChainArgs A) {
             if (threadIdx.x == 0) chain_wait_count(A.ctl + 10, A.gp.Mp, A.ctl);
             __syncthreads();
           }
+          const bool pre = TRAIN && A.t4.hb != nullptr;
+          constexpr int OFF = HOFF + ChainT4Lds::HF;     // (after the head forward's scratch and weights)
+          char* dhscr = smem + OFF + ChainT4Lds::DHT;
+          // the mask's partial sums (the loss gradient's 1 / max(n, 1)) as well: the labels are complete
+          // here and the loads cost nothing during that wait; the time4 stage's barriers publish them
+          if (pre) ch_mask_partials(A.t4.hd.mask, A.t4.hd.M, ch_head_dh_red<128>(dhscr));
           chain_t4_stage<TRAIN>(A.t4, r, A.ntiles, A.Mp, tagb, A.ctl, smem);
           long long* mk = blockIdx.x < 64 ? A.trace + 512 + blockIdx.x : nullptr;   // (trace: phase ends)
           if (mk != nullptr && threadIdx.x == 0) mk[0] = (long long)__builtin_amdgcn_s_memrealtime();
           if (threadIdx.x >= 64 * CH_NW) return;    // the head runs on 8 waves (the rest exit)
-          const bool pre = TRAIN && A.t4.hb != nullptr;
+          ChainHeadKeep keep;
           chain_head_fwd<128>(A.t4.hd, r, A.ntiles, reinterpret_cast<const float*>(smem + ChainT4Lds::HS + ChainT4Lds::XS),
-                              smem + HOFF, true, !pre);
+                              smem + HOFF, true, !pre, pre ? ch_head_dh_sz1<128>(dhscr) : nullptr, &keep);
           if (mk != nullptr && threadIdx.x == 0) mk[64] = (long long)__builtin_amdgcn_s_memrealtime();
           if constexpr (TRAIN) {
             if (A.t4.hb != nullptr) {
-              // the head backward, here instead of at the start of the backward launch (it only needs
-              // this launch's outputs; dL/dloss = 1, scaled there): the backward's time4 stage then
-              // starts its reverse steps at once (the head backward was ~12 us of its critical path)
-              __syncthreads();
-              constexpr int OFF = HOFF + ChainT4Lds::HF;   // (after the head forward's scratch and weights)
+              // the hand-over to the backward launch: the head forward above continues into the
+              // backward-to-dh (it kept z1, a1, z2 and the logit; dL/dloss = 1, scaled there), so the
+              // backward's time4 stage starts its reverse steps at once. The head's weight-gradient
+              // records are NOT built here, on the step's critical path between the two recurrences:
+              // the backward launch's time4 workgroups build them after their reverse steps, where
+              // they would otherwise idle until the chain has drained (chain_t4_bwd_stage).
               float* dhs = reinterpret_cast<float*>(smem + OFF);
-              ChainHead hb = A.t4.hd;
-              hb.gpart = A.t4.hb + (size_t)A.ntiles * 16 * 128;
-              chain_head_bwd<128>(hb, reinterpret_cast<const float*>(smem + ChainT4Lds::HS + ChainT4Lds::XS), r, A.ntiles,
-                                  dhs, smem + OFF + ChainT4Lds::DHT, 132, true, false, CH_NW, hW1, hW1 + 128 * CH_WP);
+              chain_head_dh<128>(A.t4.hd, r, keep, smem + HOFF, dhscr, dhs);
+              __syncthreads();
               for (int e = ch_tid(); e < 16 * 128; e += 64 * CH_NW)
                 A.t4.hb[((size_t)r * 16 + e / 128) * 128 + e % 128] = dhs[(e / 128) * 132 + e % 128];
               // the loss hand-off last: its stores' acknowledgement wait then overlaps nothing it delays
@@ -1033,7 +1038,7 @@ struct ChainT4B {
   const float* g;                    // saved gates, fp32 (time4_head.hip t4_sidx layout)
   const float* c;                    // saved (c_t, c_{t-1})
   const bf16x8_t* pk;                // the forward's fragment image of (W, U) (lstm_chain_head_fwd)
-  const float* hb;                   // the forward's precomputed head backward (ChainT4::hb) or nullptr
+  const float* hb;                   // the forward's dh_{T-1} tiles for dL/dloss = 1 (ChainT4::hb) or nullptr
   __bf16* dz;                        // [T+1][Mp][512] bf16 (the weight-gradient pass's input)
   unsigned long long* sout;          // dx granule stream [T][Mp][Din]
   int T, Din, Dw, on;
@@ -1821,13 +1826,33 @@ __device__ __forceinline__ void chain_bwd_stage_sk(const ChainBStage S, int tile
   if constexpr (!PUBW) store_dx((T - 1) & 1, 0, tagb);     // dx tile of t = 0
 }
 
-// time4's backward on one 16-sequence tile with 1024 threads: the head backward (chain_head.h,
-// waves 8..15 repeating waves 0..7), then the reverse recurrence with two cells per lane:
+// The head's weight-gradient records of `tile`, built by the time4 backward workgroup after its
+// reverse steps (the forward launch handed over dh_{T-1} only): the head backward as it runs in the
+// other mode, its dh landing in the now free dhT tile. A function of its own that reads the kernel's
+// arguments itself (ka: the launch's kernarg segment; smem: the workgroup's LDS): inlined behind the
+// step loop, its live ranges (the whole ChainHead, thread-index arithmetic shared with the
+// prologue) cost that loop registers - 24 to 27 VGPR spills instead of 4, with reloads in every
+// reverse step, in each inlined arrangement compiled; like this the kernel's resources are the
+// same as without it.
+typedef __attribute__((address_space(4))) ChainBArgs ChainBKernArgs;
+typedef __attribute__((address_space(3))) char ChainLdsChar;
+__device__ __noinline__ void chain_t4_bwd_records(const ChainBKernArgs* ka, ChainLdsChar* smem, int tile, int ntiles,
+                                                  int Mp) {
+  using L = ChainT4BLds;
+  char* s = (char*)smem;
+  const ChainT4B& Q = ((const ChainBArgs*)ka)->t4;
+  chain_head_bwd<128>(Q.hd, Q.h + (size_t)(Q.T - 1) * Mp * 128, tile, ntiles, reinterpret_cast<float*>(s), s + L::DHT);
+}
+
+// time4's backward on one 16-sequence tile with 1024 threads: dh_{T-1} from the forward launch
+// (Q.hb, with the head backward - chain_head.h, waves 8..15 repeating waves 0..7 - run AFTER the
+// steps for its weight-gradient records) or from the head backward run first (Q.hb == nullptr),
+// then the reverse recurrence with two cells per lane:
 // dh_rec^T = U dz^T with wave w on unit tile w % 8 over K half w / 8, dx^T = W dz^T with din tile
 // w % 4 over K quarter w / 4 (partials summed through LDS), dz -> HBM, dx -> granules (tag =
 // pooled time of the chain's top layer). Then this tile's share of the head-gradient reduction.
-__device__ __forceinline__ void chain_t4_bwd_stage(const ChainT4B Q, int tile, int ntiles, int Mp, unsigned tagb,
-                                                   char* smem, long long* mk = nullptr) {
+__device__ __forceinline__ void chain_t4_bwd_stage(const ChainT4B Q, const ChainBKernArgs* kargs, int tile, int ntiles,
+                                                   int Mp, unsigned tagb, char* smem, long long* mk = nullptr) {
   constexpr int H = 128, G4 = 4 * H, NW = 16, CPL = 2, HP = H + 4, ZP = G4 + 8, XP = 68;
   using L = ChainT4BLds;
   static_assert(L::DHT % 16 == 0 && L::ZS % 16 == 0 && L::DN % 16 == 0, "t4 backward LDS layout");
@@ -1865,7 +1890,7 @@ __device__ __forceinline__ void chain_t4_bwd_stage(const ChainT4B Q, int tile, i
   };
   load_slot(0, T - 1);
   load_slot(1, T - 2);
-  if (Q.hb != nullptr) {                           // precomputed by the forward (dL/dloss = 1): scale
+  if (Q.hb != nullptr) {                           // dh_{T-1} from the forward launch (dL/dloss = 1): scale
     const float gl = Q.hd.dloss[0];
     for (int e = tid; e < 16 * H; e += 1024) dhT[(e / H) * HP + e % H] = gl * Q.hb[((size_t)tile * 16 + e / H) * H + e % H];
   } else {
@@ -1874,6 +1899,9 @@ __device__ __forceinline__ void chain_t4_bwd_stage(const ChainT4B Q, int tile, i
   // weight fragments (after the head prologue: live through it they would crowd its registers),
   // from the forward's lane-contiguous fragment image (time4_head.hip's backward layout: wave
   // w' < 8 holds unit tile w' over the full K, and din tile w' % 4 over gate-column half w' / 4)
+  // (Every prologue load before one wait - dL/dloss, both dh loads and these fragments in flight
+  // together - compiled with spill traffic inside the step loop below: not done, see
+  // profiles/chain_head_handover_ab.txt.)
   const int ut = w & 7, kh = w >> 3, dt = w & 3, kq = w >> 2;
   bf16x8_t ufr[8], wfr[4];
   {
@@ -1948,12 +1976,12 @@ __device__ __forceinline__ void chain_t4_bwd_stage(const ChainT4B Q, int tile, i
   }
   if (mk != nullptr && tid == 0) mk[64] = (long long)__builtin_amdgcn_s_memrealtime();  // (trace: steps done)
   if (Q.hb != nullptr) {
-    ChainHead hd = Q.hd;
-    hd.gpart = const_cast<float*>(Q.hb) + (size_t)ntiles * 16 * H;
-    chain_head_bwd_reduce<H>(hd, tile, ntiles, true, Q.hd.dloss[0]);
-  } else {
-    chain_head_bwd_reduce<H>(Q.hd, tile, ntiles);
+    // the head's weight-gradient records, which nothing needed before: this workgroup is done ~15 us
+    // into a launch of ~100 us
+    __syncthreads();                               // the step tiles become the head scratch
+    chain_t4_bwd_records(kargs, (ChainLdsChar*)smem, tile, ntiles, Mp);
   }
+  chain_head_bwd_reduce<H>(Q.hd, tile, ntiles);
 }
 
 __global__ __launch_bounds__(1024) void lstm_chain_bwd_kernel(ChainBArgs A) {
@@ -1963,7 +1991,9 @@ __global__ __launch_bounds__(1024) void lstm_chain_bwd_kernel(ChainBArgs A) {
   if (s == A.ns && A.t4.on && tile < A.ntiles) {  // time4 + head backward of this tile
     if (threadIdx.x == 0) A.trace[2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
     const unsigned tagb = chain_tag_base((unsigned)__hip_atomic_load(A.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    chain_t4_bwd_stage(A.t4, tile, A.ntiles, A.Mp, tagb, smem, blockIdx.x < 64 ? A.trace + 512 + blockIdx.x : nullptr);
+    // (A is this kernel's only explicit argument: it starts the kernarg segment)
+    chain_t4_bwd_stage(A.t4, (const ChainBKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), tile, A.ntiles, A.Mp, tagb,
+                       smem, blockIdx.x < 64 ? A.trace + 512 + blockIdx.x : nullptr);
     __syncthreads();
     if (threadIdx.x == 0) A.trace[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();
     chain_finish(A.ctl, nblk);
@@ -2291,10 +2321,11 @@ static std::vector<at::Tensor> chain_fwd_impl(const at::Tensor& x, at::TensorLis
     t4_head_fwd_args(Q.hd, t4->head, *t4->y, *t4->mask, t4->M, Mp, t4->alpha1, t4->alpha2, t4->w0, t4->w1, t4->sums,
                      t4->hist, logits, loss, part);
     t4out = {h4, g4, c4, logits, loss, part};
-    // the head backward precomputed by this launch (GNNQC_HEAD_BWD_IN_FWD=0: the backward runs it)
+    // the head's dh_{T-1} computed by this launch (GNNQC_HEAD_BWD_IN_FWD=0: the backward launch runs
+    // the whole head backward before its reverse steps)
     const char* hbe = std::getenv("GNNQC_HEAD_BWD_IN_FWD");
     if (train && !(hbe != nullptr && hbe[0] == '0')) {
-      hb_t = at::empty({(long)ntiles * 16 * 128 + (long)ntiles * ChainHeadRec<128>::PITCH}, opt);
+      hb_t = at::empty({(long)ntiles * 16 * 128}, opt);
       Q.hb = hb_t.data_ptr<float>();
     } else {
       hb_t = at::empty({0}, opt);
@@ -2431,8 +2462,7 @@ std::vector<at::Tensor> lstm_chain_head_bwd(const at::Tensor& dloss, const at::T
   Q.pk = reinterpret_cast<const bf16x8_t*>(pk.data_ptr());
   if (hb.numel() > 0) {
     check_f32_cuda(hb, "lstm_chain_head_bwd hb");
-    TORCH_CHECK(hb.numel() == (long)(Mp / 16) * 16 * 128 + (long)(Mp / 16) * ChainHeadRec<128>::PITCH,
-                "lstm_chain_head_bwd: hb must be the forward's precomputed head backward");
+    TORCH_CHECK(hb.numel() == (long)(Mp / 16) * 16 * 128, "lstm_chain_head_bwd: hb must be the forward's dh tiles");
     Q.hb = hb.data_ptr<float>();
   } else {
     Q.hb = nullptr;

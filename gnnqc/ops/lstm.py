@@ -457,7 +457,7 @@ class _HipLSTMChainHead(torch.autograd.Function):
                                            sums_, hist_)
             h4, g4, c4, logits, loss = outs[-5:]
             del outs[-5:]
-            hb = outs.pop()       # the head backward precomputed by the launch (dL/dloss = 1), or empty
+            hb = outs.pop()       # the head's dh_{T-1} computed by the launch (dL/dloss = 1), or empty
             pk = outs.pop()
         else:
             # (the chain's spare workgroups build time4's weight-fragment image on the way)
