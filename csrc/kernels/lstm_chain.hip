@@ -30,6 +30,7 @@
 // Each stage also writes everything the per-layer kernels write (h, gate / cell state for
 // the backward, pooled output + argmax bytes), so the backward is unchanged.
 #include "chain_head.h"
+#include "chain_wgrad.h"
 #include "common.h"
 #include "gcn_fused.h"
 #include "lstm_grads_body.h"
@@ -1051,6 +1052,9 @@ struct ChainBArgs {
   int* ctl;
   long long* trace;
   ChainT4B t4;                       // t4.on: blocks [ns nt8, (ns + 1) nt8) run time4's backward
+  // weight-gradient epilogues (chain_wgrad.h) of stage s / [CHAIN_MAX]: time4. Appended: ChainBStage and the
+  // offsets of every field above stay where they were (profiles/chain_variant_retirement.txt)
+  ChainWJob wj[CHAIN_MAX + 1];
 };
 static_assert(sizeof(ChainBArgs) <= 4096, "chain backward kernel arguments");
 
@@ -1102,6 +1106,8 @@ struct ChainT4BLds {
   static constexpr int BYTES = DHT + (STEP > HEAD ? STEP : HEAD);
 };
 static constexpr int CHAINB_LDS = ChainT4BLds::BYTES > CHAINB_LDS_STAGE ? ChainT4BLds::BYTES : CHAINB_LDS_STAGE;
+static_assert(ChainWLds<32>::BYTES <= CHAINB_LDS && ChainWLds<64>::BYTES <= CHAINB_LDS &&
+                  ChainWLds<128>::BYTES <= CHAINB_LDS, "the weight-gradient epilogue runs in the stages' LDS");
 
 #ifndef CHAINB_LEAD
 #define CHAINB_LEAD 1
@@ -1844,6 +1850,36 @@ __device__ __noinline__ void chain_t4_bwd_records(const ChainBKernArgs* ka, Chai
   chain_head_bwd<128>(Q.hd, Q.h + (size_t)(Q.T - 1) * Mp * 128, tile, ntiles, reinterpret_cast<float*>(s), s + L::DHT);
 }
 
+// The weight-gradient record of (layer, tile), built by the layer's backward workgroup after its reverse
+// steps (chain_wgrad.h): job = the stage index, CHAIN_MAX for time4; hidden size H. Like
+// chain_t4_bwd_records a function of its own that reads the launch's kernarg segment itself, so that the
+// step loops in front of it keep their registers. Every live thread of the workgroup calls it. The
+// barrier in front drains the workgroup's dz stores and makes them visible to its own loads (workgroup
+// scope: one CU, one vector L1, which has not held these lines before), and frees the stage's LDS.
+static __device__ __noinline__ void chain_wgrad_epilogue(const ChainBKernArgs* ka_v, ChainLdsChar* smem, int job_v,
+                                                         int H_v, int tile_v) {
+  const unsigned long long kp = (unsigned long long)ka_v;
+  const ChainBKernArgs* ka = (const ChainBKernArgs*)(
+      ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(kp >> 32)) << 32) |
+      (unsigned)__builtin_amdgcn_readfirstlane((int)kp));
+  // (arguments of a call arrive in vector registers: made scalar again, the job record is read with scalar
+  // loads from the kernarg segment and every branch on it is uniform)
+  const int job = __builtin_amdgcn_readfirstlane(job_v), H = __builtin_amdgcn_readfirstlane(H_v);
+  const int tile = __builtin_amdgcn_readfirstlane(tile_v);
+  const __attribute__((address_space(4))) ChainWJob* J = &ka->wj[job];
+  if (!J->on) return;                              // (frozen weights, or the switch is off)
+  __syncthreads();
+  const float* x = J->x;
+  const float* h = J->h;
+  const __bf16* dz = J->dz;
+  float* ws = J->ws;
+  const long x_elems = J->x_elems;
+  const int ldx = J->ldx, T = J->T, Dw = J->Din, Mp = ka->Mp;
+  if (H == 32) chain_wgrad_body<32>(x, h, dz, ws, x_elems, ldx, T, Dw, Mp, tile, (char*)smem);
+  else if (H == 64) chain_wgrad_body<64>(x, h, dz, ws, x_elems, ldx, T, Dw, Mp, tile, (char*)smem);
+  else if (H == 128) chain_wgrad_body<128>(x, h, dz, ws, x_elems, ldx, T, Dw, Mp, tile, (char*)smem);
+}
+
 // time4's backward on one 16-sequence tile with 1024 threads: dh_{T-1} from the forward launch
 // (Q.hb, with the head backward - chain_head.h, waves 8..15 repeating waves 0..7 - run AFTER the
 // steps for its weight-gradient records) or from the head backward run first (Q.hb == nullptr),
@@ -1981,6 +2017,8 @@ __device__ __forceinline__ void chain_t4_bwd_stage(const ChainT4B Q, const Chain
     __syncthreads();                               // the step tiles become the head scratch
     chain_t4_bwd_records(kargs, (ChainLdsChar*)smem, tile, ntiles, Mp);
   }
+  // time4's own weight-gradient record of this tile (the other tiles' head records arrive meanwhile)
+  chain_wgrad_epilogue(kargs, (ChainLdsChar*)smem, CHAIN_MAX, H, tile);
   chain_head_bwd_reduce<H>(Q.hd, tile, ntiles);
 }
 
@@ -2041,6 +2079,10 @@ __global__ __launch_bounds__(1024) void lstm_chain_bwd_kernel(ChainBArgs A) {
 #undef GQ_CHAINB_STAGE_16
 #undef GQ_CHAINB_STAGE_32
 #undef GQ_CHAINB_STAGE_64
+  // an upper stage's weight-gradient record of this tile; the H = 16 stages run to the launch's end and
+  // leave theirs to the tail launch (lstm_grads_multi)
+  if (H != 16)
+    chain_wgrad_epilogue((const ChainBKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), (ChainLdsChar*)smem, s, H, tile);
   __syncthreads();
   if (threadIdx.x == 0) A.trace[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();
   chain_finish(A.ctl, nblk);
@@ -2404,12 +2446,60 @@ static std::vector<at::Tensor> chain_bwd_setup(ChainBArgs& A, std::vector<at::Te
                                                at::TensorList pidx, at::IntArrayRef pool, at::IntArrayRef x_width,
                                                at::IntArrayRef T_in, int extra_blocks);
 
+// The weight-gradient epilogue of one backward workgroup row (chain_wgrad.h): x / h the layer's input and output
+// of the forward, dz the stage's own, ws a workspace of exactly ntiles records (lstm_grads_record_ws).
+static ChainWJob chain_wgrad_job(const at::Tensor& x, const at::Tensor& h, const __bf16* dz, const at::Tensor& ws,
+                                 const at::Tensor& W, int H, int T, int Mp) {
+  check_f32_cuda(h, "lstm_chain_bwd weight-gradient h");
+  check_f32_cuda(ws, "lstm_chain_bwd weight-gradient workspace");
+  const int Dw = (int)W.size(0), ntiles = Mp / 16;
+  TORCH_CHECK(H == 32 || H == 64 || H == 128, "lstm_chain_bwd: a weight-gradient epilogue needs H = 32, 64 or 128");
+  TORCH_CHECK(Dw >= 1 && Dw <= 64 && W.size(1) == 4 * H, "lstm_chain_bwd: weight-gradient W shape");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3 && x.size(0) == T && x.size(1) == Mp &&
+                  x.size(2) >= Dw, "lstm_chain_bwd: weight-gradient x shape");
+  const long ldx = x.stride(1);
+  TORCH_CHECK(x.stride(2) == 1 && ldx % 4 == 0 && ldx >= x.size(2) && x.stride(0) == (long)Mp * ldx &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "lstm_chain_bwd: weight-gradient x layout");
+  const long x_elems = (long)(x.storage().nbytes() / sizeof(float)) - x.storage_offset();
+  TORCH_CHECK(((long)T * Mp - 1) * ldx + (Dw + 3) / 4 * 4 <= x_elems, "lstm_chain_bwd: weight-gradient x storage");
+  TORCH_CHECK(h.numel() == (long)T * Mp * H, "lstm_chain_bwd: weight-gradient h shape");
+  TORCH_CHECK(ws.numel() == (long)ntiles * GradsGeom(H, Dw).RC,
+              "lstm_chain_bwd: the weight-gradient workspace holds one record per tile");
+  ChainWJob J{};
+  J.x = x.data_ptr<float>();
+  J.h = h.data_ptr<float>();
+  J.dz = dz;
+  J.ws = ws.data_ptr<float>();
+  J.x_elems = x_elems;
+  J.ldx = (int)ldx;
+  J.T = T;
+  J.Din = Dw;
+  J.on = 1;
+  return J;
+}
+
+// wgrad (optional): [x_s, h_s, ws_s] per stage - the layer's forward input and output and a workspace of ntiles
+// records; an empty ws_s leaves the stage's weight gradients to the caller (frozen weights, H = 16)
+static void chain_wgrad_jobs(ChainBArgs& A, const std::vector<at::Tensor>& wgrad, at::TensorList W, at::IntArrayRef T_in) {
+  TORCH_CHECK((int)wgrad.size() >= 3 * A.ns, "lstm_chain_bwd: wgrad lists [x, h, ws] per stage");
+  for (int s = 0; s < A.ns; ++s) {
+    if (wgrad[3 * s + 2].numel() == 0) continue;
+    A.wj[s] = chain_wgrad_job(wgrad[3 * s], wgrad[3 * s + 1], A.st[s].dz, wgrad[3 * s + 2], W[s], A.st[s].H, (int)T_in[s],
+                              A.Mp);
+  }
+}
+
 std::vector<at::Tensor> lstm_chain_bwd(const at::Tensor& dh, at::TensorList g, at::TensorList c, at::TensorList W,
                                        at::TensorList U, at::TensorList pidx, at::IntArrayRef pool,
-                                       at::IntArrayRef x_width, at::IntArrayRef T_in) {
+                                       at::IntArrayRef x_width, at::IntArrayRef T_in,
+                                       c10::optional<std::vector<at::Tensor>> wgrad) {
   ChainBArgs A{};
   std::vector<at::Tensor> keep;
   auto res = chain_bwd_setup(A, keep, dh, g, c, W, U, pidx, pool, x_width, T_in, 0);
+  if (wgrad.has_value()) {
+    TORCH_CHECK((int)wgrad->size() == 3 * A.ns, "lstm_chain_bwd: wgrad lists [x, h, ws] per stage");
+    chain_wgrad_jobs(A, *wgrad, W, T_in);
+  }
   hipLaunchKernelGGL(lstm_chain_bwd_kernel, dim3(A.ns * A.nt8), dim3(1024), 0, stream(), A);
   GQ_LAUNCH_CHECK();
   return res;
@@ -2433,7 +2523,8 @@ std::vector<at::Tensor> lstm_chain_head_bwd(const at::Tensor& dloss, const at::T
                                             const at::Tensor& mask, int64_t M, double alpha1, double alpha2, double w0,
                                             double w1, at::TensorList hgrads, at::TensorList g, at::TensorList c,
                                             at::TensorList W, at::TensorList U, at::TensorList pidx,
-                                            at::IntArrayRef pool, at::IntArrayRef x_width, at::IntArrayRef T_in) {
+                                            at::IntArrayRef pool, at::IntArrayRef x_width, at::IntArrayRef T_in,
+                                            c10::optional<std::vector<at::Tensor>> wgrad) {
   check_f32_cuda(x4, "x4");
   for (const at::Tensor* t : {&dloss, &h4, &g4, &c4, &Wt4, &Ut4}) check_f32_cuda(*t, "lstm_chain_head_bwd operand");
   TORCH_CHECK(x4.dim() == 3 && x4.is_contiguous(), "lstm_chain_head_bwd: x4 must be a contiguous [T4, Mp, Din]");
@@ -2475,6 +2566,12 @@ std::vector<at::Tensor> lstm_chain_head_bwd(const at::Tensor& dloss, const at::T
   Q.Dw = Dw;
   at::Tensor gpart;
   t4_head_bwd_args(Q.hd, head, y, mask, M, Mp, alpha1, alpha2, w0, w1, dloss, hgrads, gpart);
+  if (wgrad.has_value()) {       // the stages' [x, h, ws], then time4's ws (its x and h are x4 / h4)
+    TORCH_CHECK((int)wgrad->size() == 3 * A.ns + 1, "lstm_chain_head_bwd: wgrad lists [x, h, ws] per stage + time4's ws");
+    chain_wgrad_jobs(A, *wgrad, W, T_in);
+    const at::Tensor& ws4 = (*wgrad)[3 * A.ns];
+    if (ws4.numel() > 0) A.wj[CHAIN_MAX] = chain_wgrad_job(x4, h4, Q.dz, ws4, Wt4, 128, T4, Mp);
+  }
   hipLaunchKernelGGL(lstm_chain_bwd_kernel, dim3((A.ns + 1) * A.nt8), dim3(1024), 0, stream(), A);
   GQ_LAUNCH_CHECK();
   res.insert(res.begin(), dz4);

@@ -80,9 +80,15 @@ struct MultiRed {
   int* nf;                         // non-finite gradient flag (chain control word 7)
 };
 
+// HMAX: the largest hidden size among the launch's jobs. The kernel is allocated for its largest instance
+// (HMAX = 128: 155 VGPRs + 52 AGPRs, 27 KB of LDS, two workgroups per CU), so the tail launch behind a chain
+// backward that built the upper layers' records itself (chain_wgrad.h) - H = 16 jobs and the GCN backward
+// only - takes the instance that holds nothing else and is resident in one round.
+template <int HMAX>
 __global__ __launch_bounds__(256) void lstm_grads_multi_kernel(MultiGrad M) {
-  __shared__ __attribute__((aligned(16))) char smem[GradsLds<128, 5>::BYTES];   // the largest instance
-  static_assert(GcnBwdLds<2, 16>::BYTES <= GradsLds<128, 5>::BYTES, "GCN job LDS");
+  constexpr int LDSB = GradsLds<HMAX, 5>::BYTES > GcnBwdLds<2, 16>::BYTES ? GradsLds<HMAX, 5>::BYTES
+                                                                          : GcnBwdLds<2, 16>::BYTES;
+  __shared__ __attribute__((aligned(16))) char smem[LDSB];   // the largest instance
   if ((int)blockIdx.x < M.gcn_nb) {                      // the GCN backward's workgroups
     const int gb = blockIdx.x;
     if (M.gcn_coef) gcn_coef_bwd_body<2, 16>(M.gcnc, gb);
@@ -97,9 +103,10 @@ __global__ __launch_bounds__(256) void lstm_grads_multi_kernel(MultiGrad M) {
   const int gb = b - M.start[k];
 #define GQ_MG(HG, DT)                                                                                    \
   case HG * 8 + DT:                                                                                      \
-    lstm_grads_body<HG, DT, 4>(gj.dz, gj.x, gj.h, gj.W, nullptr, gj.ws, gj.rows, gj.period, gj.hshift, gj.Din, \
-                               gj.ldx, 0, gj.Din, gj.xg, gj.x_elems, gb % gj.ncb, gb / gj.ncb, gj.ncb, gj.splits, \
-                               smem);                                                                    \
+    if constexpr (HG <= HMAX)                                                                            \
+      lstm_grads_body<HG, DT, 4>(gj.dz, gj.x, gj.h, gj.W, nullptr, gj.ws, gj.rows, gj.period, gj.hshift, gj.Din, \
+                                 gj.ldx, 0, gj.Din, gj.xg, gj.x_elems, gb % gj.ncb, gb / gj.ncb, gj.ncb, gj.splits, \
+                                 smem);                                                                  \
     break;
 #define GQ_MG_H(HG) GQ_MG(HG, 1) GQ_MG(HG, 2) GQ_MG(HG, 3) GQ_MG(HG, 4) GQ_MG(HG, 5)
   switch (M.key[k]) {
@@ -141,6 +148,17 @@ at::Tensor lstm_grads_job_ws(const at::Tensor& dz, const at::Tensor& x, const at
                                                             (long)PIPE_MAX_SPLITS}));
   c10::DeviceGuard guard(x.device());
   return at::empty({(long)splits * geo.RC}, x.options());
+}
+
+// workspace of exactly `splits` records of the layer with input weights W [Din, 4H]: the backward chain's
+// weight-gradient epilogues write one per 16-sequence tile (chain_wgrad.h)
+at::Tensor lstm_grads_record_ws(const at::Tensor& W, int64_t splits) {
+  check_f32_cuda(W, "W");
+  TORCH_CHECK(W.dim() == 2 && W.size(1) % 64 == 0 && splits >= 1 && splits <= PIPE_MAX_SPLITS,
+              "lstm_grads_record_ws: W [Din, 4H] and 1 .. ", PIPE_MAX_SPLITS, " records");
+  const GradsGeom geo((int)W.size(1) / 4, (int)W.size(0));
+  c10::DeviceGuard guard(W.device());
+  return at::empty({splits * (long)geo.RC}, W.options());
 }
 
 static bool grads_job_ok(const at::Tensor& x, int Dw) {
@@ -265,7 +283,7 @@ void lstm_grads_multi(at::TensorList gz, at::TensorList gx, at::TensorList gh, a
                           gcn_t[14], gcn_t[15], gcn_t[16], gcn_t[17], gcn_t[18], gcn_t[19], gcn_t[20], M.gcn_nb);
       TORCH_CHECK(M.gcn.key == 2 * 64 + 16, "lstm_grads_multi: the GCN job takes 2 input / 16 output channels");
     }
-    int nb = 0;
+    int nb = 0, hmax = 16;
     std::vector<at::Tensor> zb(ng);      // rounded dz of fp32 jobs; stream-ordered, so the temporaries may go
     for (int k = 0; k < ng; ++k) {
       check_dz_cuda(gz[k]);
@@ -279,9 +297,11 @@ void lstm_grads_multi(at::TensorList gz, at::TensorList gx, at::TensorList gh, a
       M.key[k] = HG * 8 + GradsGeom::din_tiles(Dw);
       M.start[k] = nb;
       nb += M.j[k].nblocks;
+      hmax = std::max(hmax, HG);
     }
     M.start[ng] = nb;
-    hipLaunchKernelGGL(lstm_grads_multi_kernel, dim3(M.gcn_nb + nb), dim3(256), 0, st, M);
+    if (hmax == 16) hipLaunchKernelGGL(lstm_grads_multi_kernel<16>, dim3(M.gcn_nb + nb), dim3(256), 0, st, M);
+    else hipLaunchKernelGGL(lstm_grads_multi_kernel<128>, dim3(M.gcn_nb + nb), dim3(256), 0, st, M);
     GQ_LAUNCH_CHECK();
   }
   if (nr) {
@@ -373,5 +393,6 @@ TORCH_LIBRARY_IMPL(gnnqc, CUDA, m) {
   m.impl("lstm_tm_grads", &gq::lstm_tm_grads);
   m.impl("lstm_tm_bwd_pipe", &gq::lstm_tm_bwd_pipe);
   m.impl("lstm_grads_job_ws", &gq::lstm_grads_job_ws);
+  m.impl("lstm_grads_record_ws", &gq::lstm_grads_record_ws);
   m.impl("lstm_grads_multi", &gq::lstm_grads_multi);
 }

@@ -49,11 +49,11 @@ TORCH_LIBRARY(gnnqc, m) {
   m.def("lstm_chain_trace(Tensor like) -> Tensor");
   m.def("lstm_chain_prof(Tensor like) -> Tensor");
   m.def("lstm_chain_bwd(Tensor dh, Tensor[] g, Tensor[] c, Tensor[] W, Tensor[] U, Tensor[] pidx, int[] pool, "
-        "int[] x_width, int[] T_in) -> Tensor[]");
+        "int[] x_width, int[] T_in, Tensor[]? wgrad=None) -> Tensor[]");
   m.def("lstm_chain_head_bwd(Tensor dloss, Tensor x4, Tensor h4, Tensor g4, Tensor c4, Tensor Wt4, Tensor Ut4, "
         "Tensor pk, Tensor hb, Tensor[] head, Tensor y, Tensor mask, int M, float alpha1, float alpha2, float w0, float w1, "
         "Tensor(a!)[] hgrads, Tensor[] g, Tensor[] c, Tensor[] W, Tensor[] U, Tensor[] pidx, int[] pool, "
-        "int[] x_width, int[] T_in) -> Tensor[]");
+        "int[] x_width, int[] T_in, Tensor[]? wgrad=None) -> Tensor[]");
   m.def("time4_head_fwd(Tensor x, Tensor W, Tensor U, Tensor b, Tensor pk, bool train, Tensor[] head, Tensor y, Tensor mask, "
         "int M, float alpha1, float alpha2, float w0, float w1, Tensor(a!) sums, Tensor(b!) hist) -> Tensor[]");
   m.def("time4_head_bwd(Tensor dloss, Tensor x, Tensor h, Tensor g, Tensor c, Tensor W, Tensor U, Tensor pk, Tensor[] head, "
@@ -68,6 +68,7 @@ TORCH_LIBRARY(gnnqc, m) {
         "Tensor gh, Tensor gW, int g_period, int g_hshift, Tensor gws, Tensor rws, Tensor rW, Tensor(a!) rdW, "
         "Tensor(b!) rdU, Tensor(c!) rdb) -> Tensor");
   m.def("lstm_grads_job_ws(Tensor dz, Tensor x, Tensor W, int H) -> Tensor");
+  m.def("lstm_grads_record_ws(Tensor W, int splits) -> Tensor");
   m.def("lstm_tm_bwd(Tensor dh, Tensor g, Tensor c, Tensor x, Tensor h, Tensor W, Tensor U, Tensor b, Tensor(a!) dW, "
         "Tensor(b!) dU, Tensor(c!) db, bool need_dx, Tensor? pidx=None, int pool=0) -> Tensor");
   // fused GeneralConv + BatchNorm + PReLU + node pooling (gcn.hip)

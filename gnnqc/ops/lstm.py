@@ -83,7 +83,35 @@ class _Pipe:
     job = None      # layer whose weight-gradient pass has not run yet
     red = None      # layer whose gradient pass ran; its split reduction has not
     batch = []      # jobs of a chain backward: all gradient passes in one launch at the flush
+    reds = []       # layers whose records the chain backward built itself: reduce-only entries of that flush
     gcn = None      # (gcn_t, gcn_i): the fused GCN backward, run as extra workgroups of that launch
+
+
+class _ChainWgrad:
+    on = None       # GNNQC_CHAIN_WGRAD, read once per process (tests set it)
+
+
+def _chain_wgrad_on() -> bool:
+    """The upper layers' (H = 32 / 64 chain stages, time4) weight-gradient records are built by their
+    own workgroups of the chain backward launch (``chain_wgrad.h``; ``GNNQC_CHAIN_WGRAD``, default
+    on) instead of by jobs of the ``lstm_grads_multi`` launch behind it."""
+    if _ChainWgrad.on is None:
+        import os
+        _ChainWgrad.on = os.environ.get("GNNQC_CHAIN_WGRAD", "1") == "1"
+    return _ChainWgrad.on
+
+
+def _chain_wgrad_ws(x, h, W, sinks, need_w):
+    """The workspace (one record per 16-sequence tile) of a chain layer whose weight gradients its own
+    backward workgroups can build, or None: the layer keeps its job of the tail launch (an H = 16
+    layer: the critical path; frozen weights; gradient buffers or an input layout the jobs do not take)."""
+    H = W.shape[1] // 4
+    if not (_chain_wgrad_on() and H in (32, 64, 128) and any(need_w) and _pipe_on(sinks, h.shape[1])
+            and _pipe_x_ok(x, W.shape[0]) and W.shape[0] <= 64 and x.dim() == 3
+            and x.stride(0) == x.shape[1] * x.stride(1)):
+        return None
+    from ..utils.native import hip_ops
+    return hip_ops().lstm_grads_record_ws(W, h.shape[1] // 16)
 
 
 # Largest sequence count (rows of 16-sequence tiles) a recurrence may have for its layer to
@@ -143,17 +171,17 @@ def defer_to_grads_launch(gcn_lists) -> bool:
 def pipe_flush():
     """Run all pending weight-gradient / reduction work (end of the backward). With a chain
     backward's batch: every pending gradient pass in ONE launch, every reduction in one more."""
-    if _Pipe.batch:
+    if _Pipe.batch or _Pipe.reds:
         from ..utils.native import hip_ops
         grads = ([_Pipe.job] if _Pipe.job is not None else []) + _Pipe.batch
-        reds = ([_Pipe.red] if _Pipe.red is not None else []) + grads
+        reds = ([_Pipe.red] if _Pipe.red is not None else []) + _Pipe.reds + grads
         gt, gi = _Pipe.gcn if _Pipe.gcn is not None else ([], [])
         hip_ops().lstm_grads_multi([j["dz"] for j in grads], [j["x"] for j in grads], [j["h"] for j in grads],
                                    [j["W"] for j in grads], [j["period"] for j in grads],
                                    [j["hshift"] for j in grads], [j["ws"] for j in grads],
                                    [r["ws"] for r in reds], [r["W"] for r in reds], [r["g"][0] for r in reds],
                                    [r["g"][1] for r in reds], [r["g"][2] for r in reds], gt, gi)
-        _Pipe.job, _Pipe.red, _Pipe.batch, _Pipe.gcn = None, None, [], None
+        _Pipe.job, _Pipe.red, _Pipe.batch, _Pipe.reds, _Pipe.gcn = None, None, [], [], None
     while _Pipe.job is not None or _Pipe.red is not None:
         _pipe_drain_one()
 
@@ -221,7 +249,7 @@ def direct_grad_accumulation(flag: bool = True):
         yield
     finally:
         _DirectGrad.enabled = prev
-        if _Pipe.job is not None or _Pipe.red is not None or _Pipe.batch:
+        if _Pipe.job is not None or _Pipe.red is not None or _Pipe.batch or _Pipe.reds:
             pipe_flush()
         _Pipe.gcn = None
         if _Deferred.pending:
@@ -388,19 +416,29 @@ class _HipLSTMChain(torch.autograd.Function):
             # of the bottom one), then the weight-gradient passes
             order = list(reversed(range(ns)))
             e8 = x.new_zeros(0, dtype=torch.uint8)
+            allsinks = {i: [_grad_sink(p) for p in ctx.params[3 * i:3 * i + 3]] for i in order
+                        if any(need[2 + 3 * i:5 + 3 * i])}
+            # layers whose own backward workgroups build their weight-gradient records inside the launch
+            wws = {i: _chain_wgrad_ws(layer_x(i), outs[5 * i], Ws[i], allsinks[i], need[2 + 3 * i:5 + 3 * i])
+                   if i in allsinks else None for i in order}
+            e = x.new_zeros(0)
+            wgrad = None if all(w is None for w in wws.values()) else \
+                [t for i in order for t in (layer_x(i), outs[5 * i], wws[i] if wws[i] is not None else e)]
             res = ops.lstm_chain_bwd(dh, [outs[5 * i + 1] for i in order], [outs[5 * i + 2] for i in order],
                                      [Ws[i] for i in order], [Us[i] for i in order],
                                      [outs[5 * i + 4] if pools[i] else e8 for i in order],
                                      [pools[i] for i in order], [layer_x(i).shape[-1] for i in order],
-                                     [outs[5 * i].shape[0] for i in order])
+                                     [outs[5 * i].shape[0] for i in order], *(() if wgrad is None else (wgrad,)))
             for k, i in enumerate(order):
                 nw = need[2 + 3 * i:5 + 3 * i]
                 if not any(nw):
                     continue
                 h = outs[5 * i]
                 xi = layer_x(i)
-                sinks = [_grad_sink(p) for p in ctx.params[3 * i:3 * i + 3]]
-                if (_pipe_on(sinks, h.shape[1]) and _pipe_x_ok(xi, Ws[i].shape[0])
+                sinks = allsinks[i]
+                if wws[i] is not None:
+                    _Pipe.reds.append(dict(ws=wws[i], W=Ws[i], g=[s for s, _ in sinks]))
+                elif (_pipe_on(sinks, h.shape[1]) and _pipe_x_ok(xi, Ws[i].shape[0])
                         and len(_Pipe.batch) < _MULTI_MAX - 2):
                     _Pipe.batch.append(_pipe_job(res[k], xi, h, Ws[i], sinks, h.shape[0] * h.shape[1], h.shape[1]))
                 else:
@@ -430,8 +468,16 @@ class _HipLSTMChainHead(torch.autograd.Function):
     the six pipelined time-major layers as ONE chain kernel (``lstm_chain.hip``), then time4
     (H = 128, last state) with the Dense head, the loss and the metric accumulation as ONE
     kernel (``time4_head.hip``); backward: the head backward + time4's reverse recurrence as ONE
-    kernel, whose dx (gradient of the chain's pooled output) feeds ONE chain backward. The
-    weight-gradient passes of all seven layers then run as one ``lstm_grads_multi`` launch.
+    kernel, whose dx (gradient of the chain's pooled output) feeds ONE chain backward.
+
+    Weight gradients: the H = 32 / 64 layers' and time4's backward workgroups are done 30 - 60 us into
+    a launch that the two H = 16 stages hold open for ~100 us, so each builds the dW | db and dU
+    record of its own 16-sequence tile after its reverse steps (``chain_wgrad.h``,
+    ``GNNQC_CHAIN_WGRAD``, default on) and the ``lstm_grads_multi`` launch behind the chain only
+    reduces those; the two H = 16 layers' passes (and the GCN backward) still run in that launch, now
+    alone, and all seven reductions in one more. (In-launch chain weight gradients were rejected in
+    rounds 3 and 5 for the critical-path stages: the H = 16 stages' post-pass lengthened the launch.
+    They still have none. With the switch off all seven passes run in the ``lstm_grads_multi`` launch.)
 
     Inputs: x [T, Mp, C] time-major, y / mask [M]; ``consts`` = (alpha1, alpha2, w0, w1);
     params = 7 x (W, U, b) then the head's (W1, b1, W2, b2, W3, b3). Returns (loss, logits [M])."""
@@ -510,21 +556,31 @@ class _HipLSTMChainHead(torch.autograd.Function):
                       [outs[5 * i].shape[0] for i in order])
         grads = [None] * npar
         sinks = {i: [_grad_sink(p) for p in ctx.params[3 * i:3 * i + 3]] for i in range(ns + 1)}
-        if _t4_chain_on() and pools[-1] == 3 and xt.is_contiguous():
+        hs = {i: outs[5 * i] for i in order}
+        hs[ns] = h4
+        t4_chain = _t4_chain_on() and pools[-1] == 3 and xt.is_contiguous()
+        # layers whose own backward workgroups build their weight-gradient records inside the chain launch
+        wws = {i: _chain_wgrad_ws(layer_x(i), hs[i], Ws[i], sinks[i], need[8 + 3 * i:11 + 3 * i])
+               for i in (order + [ns] if t4_chain else order)}
+        e = x.new_zeros(0)
+        wgrad = [t for i in order for t in (layer_x(i), hs[i], wws[i] if wws[i] is not None else e)]
+        if t4_chain:
+            wgrad.append(wws[ns] if wws[ns] is not None else e)
+        # (the argument is left out when no layer is on: the call as it was)
+        wopt = () if all(w is None for w in wws.values()) else (wgrad,)
+        if t4_chain:
             # time4 + head backward as the first stage of the chain backward launch: the top
             # chain stage consumes time4's dx as it is produced
             res = ops.lstm_chain_head_bwd(g, xt, h4, g4, c4, Ws[ns], Us[ns], pk, hb, list(head), y, mask, ctx.M, *ctx.consts,
-                                          [s for s, _ in hsinks], *chain_args)
+                                          [s for s, _ in hsinks], *chain_args, *wopt)
             dz4 = res.pop(0)
         else:
             dz4, dxt = ops.time4_head_bwd(g, xt, h4, g4, c4, Ws[ns], Us[ns], pk, list(head), y, mask, ctx.M,
                                           *ctx.consts, [s for s, _ in hsinks])
-            res = ops.lstm_chain_bwd(dxt, *chain_args)
+            res = ops.lstm_chain_bwd(dxt, *chain_args, *wopt)
         dzs = {ns: dz4}
-        hs = {ns: h4}
         for k, i in enumerate(order):
             dzs[i] = res[k]
-            hs[i] = outs[5 * i]
         for i in [ns] + order:
             nw = need[8 + 3 * i:11 + 3 * i]
             if not any(nw):
@@ -532,7 +588,10 @@ class _HipLSTMChainHead(torch.autograd.Function):
             h = hs[i]
             xi = layer_x(i)
             sk = sinks[i]
-            if (_pipe_on(sk, h.shape[1]) and _pipe_x_ok(xi, Ws[i].shape[0])
+            if wws.get(i) is not None:
+                # the records are there: a reduce-only entry of the flush
+                _Pipe.reds.append(dict(ws=wws[i], W=Ws[i], g=[s for s, _ in sk]))
+            elif (_pipe_on(sk, h.shape[1]) and _pipe_x_ok(xi, Ws[i].shape[0])
                     and len(_Pipe.batch) < _MULTI_MAX - 2):
                 _Pipe.batch.append(_pipe_job(dzs[i], xi, h, Ws[i], sk, h.shape[0] * h.shape[1], h.shape[1]))
             else:
