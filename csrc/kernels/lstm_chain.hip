@@ -61,6 +61,9 @@ static constexpr int CHAIN_SPIN = 1 << 20;
 #define CHAIN_D3 2           // ring of a pooling (PIN = 3) consumer: it runs at a third of the rate
 #endif                       // (2 vs 3: 0.2982 0.2994 vs 0.3022 0.3027 ms/step; the backward rings at 3
                              // instead of 4 and LEAD3 = 0 were slower: 0.3054 0.3057, 0.3043)
+#ifndef CHAIN_D16S
+#define CHAIN_D16S 4         // ring of the H = 16 non-pooling stream consumer, the one stage that runs at its producer's rate
+#endif
 #ifndef CHAIN_LEAD1
 #define CHAIN_LEAD1 1
 #endif
@@ -210,6 +213,8 @@ __device__ __forceinline__ void chain_wait_count(const int* p, int n, int* ctl) 
 // and conditional stores kept the compiler from overlapping the step phases (chain forward 107 ->
 // 131 us, backward 124 -> 155 us, measured).
 static constexpr int CHAIN_PROF_STEPS = 64;
+// (one more row per stage: word 0 counts the stage's re-poll rounds, all tiles)
+static constexpr int CHAIN_PROF_ROWS = CHAIN_PROF_STEPS + 1;
 #ifdef GQ_CHAIN_PROF
 __device__ __forceinline__ void chain_mark(long long* pr, int step, int k) {
   if (pr != nullptr && threadIdx.x == 0 && step < CHAIN_PROF_STEPS)
@@ -220,9 +225,16 @@ __device__ __forceinline__ void chain_mark_wave(long long* pr, int step, int k) 
   if (pr != nullptr && (threadIdx.x & 63) == 0 && step < CHAIN_PROF_STEPS)
     pr[step * 8 + k] = (long long)__builtin_amdgcn_s_memtime();
 }
+// (a clock read now, stored later: a mark's store must not sit in front of a wait that is being measured)
+__device__ __forceinline__ long long chain_clock() { return (long long)__builtin_amdgcn_s_memtime(); }
+__device__ __forceinline__ void chain_mark_wave_at(long long* pr, int step, int k, long long v) {
+  if (pr != nullptr && (threadIdx.x & 63) == 0 && step < CHAIN_PROF_STEPS) pr[step * 8 + k] = v;
+}
 #else
 __device__ __forceinline__ void chain_mark(long long*, int, int) {}
 __device__ __forceinline__ void chain_mark_wave(long long*, int, int) {}
+__device__ __forceinline__ long long chain_clock() { return 0; }
+__device__ __forceinline__ void chain_mark_wave_at(long long*, int, int, long long) {}
 #endif
 
 // Tag base of a launch: (epoch mod (2^20 - 1)) + 1 in the high 20 bits of the 32-bit tag, the
@@ -264,7 +276,8 @@ __device__ __forceinline__ float chain_gate_scale(int ag) { return ag == 2 ? -2.
 // LDS tile of the next step. (A register ring of D slots in one wave was the first form: the
 // compiler's wait insertion drained the whole ring at the top of every unrolled round.) For a last
 // stage that pools its own output, I/O wave 0 pools h from the fp32 LDS tile. One LDS barrier per
-// step. Without I/O waves every thread also streams x through a D-slot register ring, as one role.
+// step. (H = 16 stages with an unpooled input: the compute waves write the publisher's LDS copies of
+// step t at the top of step t + 1, and the publisher runs two steps behind; chain_stage LATEW.) Without I/O waves every thread also streams x through a D-slot register ring, as one role.
 // (I/O waves only when they fit the 1024-thread workgroup and a lane's share of one step's tile - ngl
 // granules of pin steps each - stays within 24 registers pairs. Every stage of the dispatch table has
 // them at the default ring depths; a deeper ring reaches the one-role form, e.g. CHAIN_D = 8 at
@@ -306,7 +319,8 @@ struct ChainCfg {
   static constexpr int NWV = H / 4, NCELL = 64 * NWV;     // the saved-state layout's waves / cells per tile
 };
 
-template <int H, bool TRAIN, int KX, int D, bool SRC, int PIN>
+// XC: channels of the x tile the I/O waves load (32 KX, or 16 for a KX = 1 stage with Din <= 16)
+template <int H, bool TRAIN, int KX, int D, bool SRC, int PIN, int XC = 32 * KX>
 __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int ntiles, int Mp, unsigned tagb,
                                             int* ctl, char* smem) {
   using C = ChainCfg<H>;
@@ -320,9 +334,14 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
   constexpr bool IOW = NIOW > 0;
   constexpr int NIO = IOW ? 64 * G : NT;         // threads streaming one step's tile
   constexpr int NSLOT = IOW ? 1 : D;             // x slots per streaming thread
-  // granules per streaming lane: I/O waves cover the largest tile the template allows; without
+  // granules per streaming lane: I/O waves cover the stage's tile class (XC channels); without
   // them every thread streams one granule (the host requires 16 Din / GR <= NT then)
-  constexpr int NGL = IOW ? (16 * KPX / GR + NIO - 1) / NIO : 1;
+  static_assert(XC <= KPX, "x tile class");
+  constexpr int NGL = IOW ? (16 * XC / GR + NIO - 1) / NIO : 1;
+  // H = 16 stages with I/O waves and an unpooled input (the bottom layer, which paces the whole chain,
+  // and the one consumer that runs at its producer's rate): the compute waves write the publisher's
+  // LDS copies of step t at the top of step t + 1, off the path from the cell to the barrier
+  constexpr bool LATEW = H == 16 && IOW && PIN == 1;
   using L = ChainLds<H, KX>;
   static_assert(L::BYTES <= CHAIN_LDS_STAGE && L::HS % 16 == 0 && L::XS % 16 == 0, "chain LDS layout");
   auto hs = reinterpret_cast<__bf16 (*)[16][C::KPH + 8]>(smem);
@@ -390,6 +409,8 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
       }
     }
   };
+  long long* pr = (S.prof != nullptr && tile == 0) ? S.prof : nullptr;
+  int mark_t = CHAIN_PROF_STEPS;                 // (profiling: the step an I/O wave's staging is clocked under)
   auto stage_x = [&](int buf, int r, int tx) {
     if constexpr (SRC) {
       // every granule's tag first (one ballot), the re-poll only on a miss
@@ -406,6 +427,8 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
         // round, not one per granule), short back-off, bounded (a timeout flags the step)
 #ifdef GQ_CHAIN_PROF
         if (lane == 0) __hip_atomic_fetch_add(ctl + 9, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0 && S.prof != nullptr)
+          __hip_atomic_fetch_add(S.prof + CHAIN_PROF_STEPS * 8, 1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
         const int lim0 = __hip_atomic_load(ctl + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int lim = lim0 > 0 ? lim0 : CHAIN_SPIN;
@@ -435,6 +458,7 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
           nap = min(nap * 2, CHAIN_RP_NAPMAX);
         }
       }
+      if (iot == 0) chain_mark_wave(pr, mark_t, 6);   // (the tile's loads are in, tags checked)
       const size_t po = xbase + (size_t)tx * xstep;
 #pragma unroll
       for (int j = 0; j < NGL; ++j) {
@@ -562,7 +586,26 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
   for (int cc = 0; cc < CPL; ++cc) c[cc] = 0.f;
   __syncthreads();
 
-  long long* pr = (S.prof != nullptr && tile == 0) ? S.prof : nullptr;
+  // (LATEW) step t - 1's outputs, carried in registers over the barrier
+  float hvl[CPL], cl[CPL];
+  uint2 gl[CPL];
+#pragma unroll
+  for (int cc = 0; cc < CPL; ++cc) {
+    hvl[cc] = cl[cc] = 0.f;
+    gl[cc] = make_uint2(0u, 0u);
+  }
+  // ... and written into the publisher's LDS buffers of step tl
+  auto late_write = [&](int tl) {
+#pragma unroll
+    for (int cc = 0; cc < CPL; ++cc) {
+      hf[tl & 1][col][unit[cc]] = hvl[cc];
+      if constexpr (TRAIN) {
+        gst[tl & 1][(wc + NW * cc) * 64 + lane] = gl[cc];
+        cst[tl & 1][(wc + NW * cc) * 64 + lane] = cl[cc];
+      }
+    }
+  };
+
   // the compute step of time t (reads xs[p], hs[p]; writes hs[p ^ 1], the outputs)
   auto compute_step = [&](int t, auto IO, int rn) {
     constexpr bool DOI = decltype(IO)::value;
@@ -580,6 +623,11 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
 #pragma unroll
       for (int s = 0; s < C::KSH; ++s) {
         const bf16x8_t bh = *reinterpret_cast<const bf16x8_t*>(&hs[p][col][32 * s + 8 * quad]);
+        // step t - 1's LDS copies for the publisher inside this read's latency, off the path to the
+        // barrier (t = 0 writes zeros into buffer 1, which step 1's copies replace before it is read)
+        if constexpr (LATEW) {
+          if (s == 0 && cc == 0) late_write(t - 1);
+        }
         acch = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ufr[cc][s], bh, acch, 0, 0, 0);
       }
       acc[cc] = accx + acch;
@@ -605,7 +653,11 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
       // polls it); the bulk outputs (h, packed gates, c) are staged in LDS for the publisher wave, whose
       // wide contiguous stores keep the CU's vector-memory path free for the consumer-side loads
       if (publish) st_granule(sp[cc] + (size_t)t * hstep, hv, tagb | (unsigned)t);
-      if constexpr (IOW) {
+      if constexpr (LATEW) {
+        hvl[cc] = hv;
+        cl[cc] = c[cc];
+        if constexpr (TRAIN) gl[cc] = gates_pack(iv, fv, gv, ov);
+      } else if constexpr (IOW) {
         hf[p][col][u] = hv;
         if constexpr (TRAIN) {
           gst[p][cell] = gates_pack(iv, fv, gv, ov);
@@ -655,11 +707,22 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
         chain_mark(pr, t, 3);
       }
       __builtin_amdgcn_s_setprio(0);
+      if constexpr (LATEW) {               // the last step's copies, behind one more barrier of all roles
+        late_write(T - 1);
+        lds_barrier();
+      }
     } else if (publisher) {
+      // LATEW: the publisher runs two steps behind (buffer t & 1 holds step t - 2 until the compute
+      // waves overwrite it at the top of step t + 1) and drains the last two steps behind the loop
+      constexpr int LAG = LATEW ? 2 : 1;
       for (int t = 0; t < T; ++t) {
-        if (t >= 1) publish_step(t - 1);
+        if (t >= LAG) publish_step(t - LAG);
         chain_mark_wave(pr, t, 7);         // (the publisher reaches the step barrier)
         lds_barrier();
+      }
+      if constexpr (LATEW) {
+        lds_barrier();
+        if (T >= 2) publish_step(T - 2);
       }
       publish_step(T - 1);
     } else {
@@ -675,15 +738,19 @@ __device__ __forceinline__ void chain_stage(const ChainStage& S, int tile, int n
           next_ld = -1;
         }
         if (kt == 0 && t + 1 < T) {
-          if (iot == 0) chain_mark_wave(pr, t, 4);
+          // (profiling: mark 4's clock is stored behind the staging. Stored at once, the mark's own store
+          // was what the staging's wait for its loads then waited for: ~450 ticks that no other build has.)
+          const long long c4 = chain_clock();
+          mark_t = t;
           stage_x((t + 1) & 1, 0, t + 1);
           if (iot == 0) chain_mark_wave(pr, t, 5);
+          if (iot == 0) chain_mark_wave_at(pr, t, 4, c4);
           next_ld = t + 1 + D;
-          if (iot == 0) chain_mark_wave(pr, t, 6);
         }
         kt = kt == 0 ? D - 1 : kt - 1;
         lds_barrier();
       }
+      if constexpr (LATEW) lds_barrier();
     }
   } else {
     for (int t0 = 0; t0 < T; t0 += D) {
@@ -981,20 +1048,28 @@ __global__ __launch_bounds__(1024) void lstm_chain_fwd_kernel(ChainArgs A) {
   const ChainStage S = A.st[s];
   const int H = S.H, KX = S.KX;
   const bool src = s > 0 || A.gp.on;              // (stage 0 then streams the GCN producers' granules)
-#define GQ_CHAIN_BODY(HH, KXX, DD, SRCV, PINV)                                          \
+#define GQ_CHAIN_BODYX(HH, KXX, DD, SRCV, PINV, XCV)                                    \
   {                                                                                     \
     constexpr int DS = chain_stage_d(HH, KXX, DD);                                      \
     if (threadIdx.x >= chain_live_threads(ChainCfg<HH>::NT, DS, KXX, SRCV, PINV, HH)) return; \
-    chain_stage<HH, TRAIN, KXX, DS, SRCV, PINV>(S, tile, A.ntiles, A.Mp, tagb, A.ctl, smem); \
+    chain_stage<HH, TRAIN, KXX, DS, SRCV, PINV, XCV>(S, tile, A.ntiles, A.Mp, tagb, A.ctl, smem); \
   }
+#define GQ_CHAIN_BODY(HH, KXX, DD, SRCV, PINV) GQ_CHAIN_BODYX(HH, KXX, DD, SRCV, PINV, 32 * KXX)
 #define GQ_CHAIN_SRC(HH, PINV, DD)                                                      \
   if (KX == 1) GQ_CHAIN_BODY(HH, 1, DD, true, PINV) else GQ_CHAIN_BODY(HH, 2, DD, true, PINV)
-#define GQ_CHAIN_KX(HH)                                                                 \
-  if (src) { if (S.PIN == 3) { GQ_CHAIN_SRC(HH, 3, CHAIN_D3) } else { GQ_CHAIN_SRC(HH, 1, CHAIN_D) } } \
+// the H = 16 non-pooling stream consumer (it runs at its producer's rate): a ring depth of its own,
+// and with Din <= 16 its I/O waves load a 16-channel tile's granules only
+#define GQ_CHAIN_SRC16                                                                  \
+  if (KX == 1 && S.Din <= 16) GQ_CHAIN_BODYX(16, 1, CHAIN_D16S, true, 1, 16) \
+  else GQ_CHAIN_SRC(16, 1, CHAIN_D16S)
+#define GQ_CHAIN_KX(HH, SRC1)                                                           \
+  if (src) { if (S.PIN == 3) { GQ_CHAIN_SRC(HH, 3, CHAIN_D3) } else { SRC1 } }          \
   else { if (KX == 1) GQ_CHAIN_BODY(HH, 1, CHAIN_D0, false, 1) else GQ_CHAIN_BODY(HH, 2, CHAIN_D0, false, 1) }
-  if (H == 16) GQ_CHAIN_KX(16)
-  else if (H == 32) GQ_CHAIN_KX(32)
-  else GQ_CHAIN_KX(64)
+  if (H == 16) GQ_CHAIN_KX(16, GQ_CHAIN_SRC16)
+  else if (H == 32) GQ_CHAIN_KX(32, GQ_CHAIN_SRC(32, 1, CHAIN_D))
+  else GQ_CHAIN_KX(64, GQ_CHAIN_SRC(64, 1, CHAIN_D))
+#undef GQ_CHAIN_SRC16
+#undef GQ_CHAIN_BODYX
 #undef GQ_CHAIN_KX
 #undef GQ_CHAIN_SRC
 #undef GQ_CHAIN_BODY
@@ -2098,7 +2173,7 @@ static long long* chain_trace_buf(int dev) {
   return tr[dev];
 }
 
-// tile 0's per-step phase clocks [CHAIN_MAX stages][CHAIN_PROF_STEPS][8] of the last launch with
+// tile 0's per-step phase clocks [CHAIN_MAX stages][CHAIN_PROF_ROWS][8] of the last launch with
 // GNNQC_CHAIN_PROF=1 (forward and backward use the same buffer)
 static long long* chain_prof_buf(int dev);
 // zero the phase-clock buffer before a profiled launch: a stage with fewer than CHAIN_PROF_STEPS
@@ -2107,7 +2182,7 @@ static long long* chain_prof_buf(int dev);
 static void chain_prof_clear(int dev) {
   long long* pb = chain_prof_buf(dev);
   if (pb != nullptr)
-    TORCH_CHECK(hipMemsetAsync(pb, 0, CHAIN_MAX * CHAIN_PROF_STEPS * 8 * sizeof(long long), stream()) == hipSuccess,
+    TORCH_CHECK(hipMemsetAsync(pb, 0, CHAIN_MAX * CHAIN_PROF_ROWS * 8 * sizeof(long long), stream()) == hipSuccess,
                 "chain prof clear");
 }
 static long long* chain_prof_buf(int dev) {
@@ -2122,8 +2197,8 @@ static long long* chain_prof_buf(int dev) {
   if (!on) return nullptr;
   static long long* pb[64] = {nullptr};
   if (!pb[dev]) {
-    TORCH_CHECK(hipMalloc(&pb[dev], CHAIN_MAX * CHAIN_PROF_STEPS * 8 * sizeof(long long)) == hipSuccess, "chain prof");
-    TORCH_CHECK(hipMemset(pb[dev], 0, CHAIN_MAX * CHAIN_PROF_STEPS * 8 * sizeof(long long)) == hipSuccess, "chain prof");
+    TORCH_CHECK(hipMalloc(&pb[dev], CHAIN_MAX * CHAIN_PROF_ROWS * 8 * sizeof(long long)) == hipSuccess, "chain prof");
+    TORCH_CHECK(hipMemset(pb[dev], 0, CHAIN_MAX * CHAIN_PROF_ROWS * 8 * sizeof(long long)) == hipSuccess, "chain prof");
   }
   return pb[dev];
 }
@@ -2133,7 +2208,7 @@ at::Tensor lstm_chain_prof(const at::Tensor& like) {
   long long* p = chain_prof_buf(like.get_device());
   TORCH_CHECK(p != nullptr, "lstm_chain_prof: build with GNNQC_CHAIN_PROF_BUILD=1 and set GNNQC_CHAIN_PROF=1 "
                             "before the first chain launch");
-  at::Tensor o = at::empty({CHAIN_MAX, CHAIN_PROF_STEPS, 8}, like.options().dtype(at::kLong));
+  at::Tensor o = at::empty({CHAIN_MAX, CHAIN_PROF_ROWS, 8}, like.options().dtype(at::kLong));
   TORCH_CHECK(hipMemcpyAsync(o.data_ptr<int64_t>(), p, o.numel() * sizeof(long long), hipMemcpyDeviceToDevice,
                              stream()) == hipSuccess, "lstm_chain_prof");
   return o;
@@ -2327,7 +2402,7 @@ static std::vector<at::Tensor> chain_fwd_impl(const at::Tensor& x, at::TensorLis
     TORCH_CHECK(s > 0 || Din % 4 == 0, "lstm_chain: the input width must be a multiple of 4");
     {
       long long* pb = chain_prof_buf(x.get_device());
-      S.prof = pb != nullptr ? pb + (size_t)s * CHAIN_PROF_STEPS * 8 : nullptr;
+      S.prof = pb != nullptr ? pb + (size_t)s * CHAIN_PROF_ROWS * 8 : nullptr;
     }
     out.insert(out.end(), {h.narrow(0, 0, T), g, c, pooled, pidx});
     if (so.defined()) out.push_back(so);        // kept alive until the launch is enqueued
@@ -2659,7 +2734,7 @@ static std::vector<at::Tensor> chain_bwd_setup(ChainBArgs& A, std::vector<at::Te
     S.trace_mid = A.trace + 512;
     {
       long long* pb = chain_prof_buf(dh.get_device());
-      S.prof = pb != nullptr ? pb + (size_t)s * CHAIN_PROF_STEPS * 8 : nullptr;
+      S.prof = pb != nullptr ? pb + (size_t)s * CHAIN_PROF_ROWS * 8 : nullptr;
     }
   }
   dzs.push_back(dx.defined() ? dx.narrow(0, 0, (int)T_in[ns - 1]) : at::empty({0}, opt));

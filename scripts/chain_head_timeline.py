@@ -45,7 +45,10 @@ def main():
         t0 = float(tt[:, 0][tt[:, 0] > 0].min())
         us = lambda v: round((float(v) - t0) / 100, 2)      # noqa: E731
         mid = t[512:768].double()
-        rows.append({"stages": [{"stage": s, "start_us": us(tt[s * nt8, 0]), "end_us": us(tt[s * nt8, 1])}
+        rows.append({"stages": [{"stage": s, "start_us": us(tt[s * nt8, 0]), "end_us": us(tt[s * nt8, 1]),
+                                 # (earliest and latest tile of the stage)
+                                 "end_min_us": us(tt[s * nt8:(s + 1) * nt8, 1].min()),
+                                 "end_max_us": us(tt[s * nt8:(s + 1) * nt8, 1].max())}
                                 for s in range(ns)],
                      # time4 workgroups: reverse... forward steps done / head forward done
                      "t4_steps_done_us": [us(mid[ns * nt8 + r]) for r in range(nt8)],

@@ -2,7 +2,9 @@
 """Per-step phase clocks of the chain kernels' stages (GNNQC_CHAIN_PROF=1; tile 0, wave 0,
 s_memtime ticks): median over the first 64 steps of every phase of the step loop, per stage.
 Forward marks (compute wave 0): 0 loop top, 1 pre-activations out of the MFMAs, 2 gates / cell /
-outputs stored, 3 after the step barrier. Backward, split-K stages (H >= 32): 0 top, 1 cell phase
+outputs stored (H = 16: and W x of the next step issued), 3 after the step barrier; I/O waves: 4
+staging start, 6 the tile's loads are in and their tags checked, 5 tile staged; 7 the publisher
+reaches the barrier. Backward, split-K stages (H >= 32): 0 top, 1 cell phase
 done, 2 next dh staged, 3 after the barrier, 4 partial products stored, 5 dh_rec ready. Backward,
 H = 16 stages (their step starts at the barrier): 0 after the barrier, 1 dh of step s + 2 staged and
 its ring load issued, 2 dh_rec (U dz) ready, 3 dz of step s + 1 written, 4 state load issued (the
@@ -77,8 +79,11 @@ def main():
                                        *hc, e.double(), e)
     torch.cuda.synchronize()
     pf = ops.lstm_chain_prof(x).cpu()
+    # (row 64 of a stage: word 0 = the re-poll rounds of its I/O waves in that launch, all tiles)
+    print(json.dumps({"launch": "fwd re-poll rounds per stage", "repolls": pf[:, 64, 0].tolist()}), flush=True)
+    pf = pf[:, :64]
     print(json.dumps({"launch": "fwd (chain6 + time4 stage)", "stages": phases(pf, 4)}), flush=True)
-    # I/O waves (marks 4..6 of the step whose x they stage: start, tile staged, next load issued),
+    # I/O waves (marks 4, 6, 5 of the step in which they stage: start, loads in, tile staged),
     # relative to compute wave 0's step start
     # (+ m7: the publisher wave reaches the step barrier)
     print(json.dumps({"launch": "fwd marks vs compute start", "stages": marks_rel(pf, 8)}), flush=True)
@@ -98,7 +103,7 @@ def main():
     for _ in range(3):
         ops.lstm_chain_head_bwd(one, xt, h4, g4, c4, Ws[6], Us[6], pk, hb, head, y, mask, M, *hc, hg, *chain_args)
     torch.cuda.synchronize()
-    pb = ops.lstm_chain_prof(x).cpu()
+    pb = ops.lstm_chain_prof(x).cpu()[:, :64]
     # (five marks per stage: the H = 16 stages write 0..4, the split-K stages 0..5, see the docstring)
     print(json.dumps({"launch": "bwd (time4 stage + chain6)", "stages": phases(pb, 5)}), flush=True)
     # H = 16 stages' I/O waves: marks 5..7 = staging start, tile staged, next loads issued
