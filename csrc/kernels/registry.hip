@@ -112,6 +112,16 @@ TORCH_LIBRARY(gnnqc, m) {
         "Tensor gamma, Tensor beta, Tensor(a!) rmean, Tensor(b!) rvar, bool training, float momentum, float eps) -> Tensor[]");
   m.def("gcn_bwd_finalize(Tensor acc, Tensor S, Tensor W, Tensor b, Tensor st, bool training, Tensor(a!) dW, "
         "Tensor(b!) db, Tensor(c!) dgamma, Tensor(d!) dbeta, Tensor(e!) dalpha) -> Tensor");
+  // fused GATConv + node pooling (gat.hip)
+  m.def("gat_adj_bits(Tensor adj, Tensor mask) -> Tensor");
+  m.def("gat_pool_fwd(Tensor x, Tensor bits, Tensor pw, Tensor anom, Tensor W, Tensor a_s, Tensor a_n, Tensor bias, "
+        "Tensor alpha, int act, int Mp=0, int Cp=0) -> Tensor");
+  m.def("gat_pool_bwd(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor W, Tensor a_s, Tensor a_n, Tensor bias, "
+        "Tensor alpha, int act, int c_off, bool time_major=False) -> Tensor");
+  m.def("gat_bwd_finalize(Tensor tot, Tensor W, Tensor a_s, Tensor a_n, Tensor(a!) dW, Tensor(b!) da_s, "
+        "Tensor(c!) da_n, Tensor(d!) dbias, Tensor(e!) dalpha) -> ()");
+  m.def("gat_pool_bwd_input(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor W, Tensor a_s, Tensor a_n, "
+        "Tensor bias, Tensor alpha, int act, int c_off, bool time_major=False) -> Tensor");
   // Conv1D + LeakyReLU (+ GAP) implicit GEMM (conv1d.hip)
   m.def("conv1d_fwd(Tensor x, Tensor W, Tensor b, float alpha, bool gap, bool store_y) -> Tensor[]");
   m.def("conv1d_bwd(Tensor dy, Tensor y, Tensor x, Tensor W, float alpha, bool gap, Tensor(a!) dW, "

@@ -25,9 +25,9 @@ import torch
 import torch.nn as nn
 
 from ..config import freq_minutes
-from ..ops.gcn import (gcn_node_tm, gcn_node_tm_ok, gcn_pool, gcn_pool_from_store, gcn_pool_hip_ok, pool_nodes,
-                       store_gcn_ok)
-from .graphconv import GeneralConv, make_graph_layer
+from ..ops.gcn import (gat_pool, gat_pool_hip_ok, gcn_node_tm, gcn_node_tm_ok, gcn_pool, gcn_pool_from_store,
+                       gcn_pool_hip_ok, pool_nodes, store_gcn_ok)
+from .graphconv import GATConv, GeneralConv, make_graph_layer
 from .layers import Dense, Dropout, LeakyReLU
 from .spatial import SensorsTimeLayer, SpatialTransformer
 from .timelayer import TimeLayer
@@ -146,6 +146,9 @@ class GCNClassifier(nn.Module):
                 return gcn_pool(feats, adj, mask, anom, anom_pos, g.kernel, g.bias, g.bn_gamma, g.bn_beta,
                                 g.prelu_alpha, g.bn_moving_mean, g.bn_moving_variance, self.training, g.aggregate,
                                 pooling, g.momentum, g.eps, g.dropout)
+            if isinstance(self.gcn_layer, GATConv):
+                # (fused HIP kernels when gat_pool_hip_ok, else the eager layer + pool_nodes + cat)
+                return gat_pool(feats, adj, mask, anom, anom_pos, self.gcn_layer, pooling)
             h = self.gcn_layer(feats, adj, mask)
             return torch.cat([anom, pool_nodes(h, mask, anom_pos, pooling)], -1)
         x, adj, mask = inputs[:3]
@@ -184,8 +187,26 @@ class GCNClassifier(nn.Module):
         return (gcn_pool_hip_ok(x, g.kernel, g.aggregate, pooling, g.dropout, self.training)
                 and self.time_layer.time_major_ok(x, g.out_features + anom.shape[-1]))
 
+    def _cml_gat_time_major(self, inputs) -> bool:
+        """CML GATConv fast path: the fused GAT + pooling kernel writes the time-major LSTM input."""
+        if not self.per_sensor or not isinstance(self.gcn_layer, GATConv) or self.sensors_time_layer is not None:
+            return False
+        if self.spatial_transformer is not None or len(inputs) > 5:
+            return False
+        x, anom = inputs[0], inputs[1]
+        pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
+        return (gat_pool_hip_ok(x, self.gcn_layer, pooling)
+                and self.time_layer.time_major_ok(x, self.gcn_layer.out_features + anom.shape[-1]))
+
+    def _gat_time_major_input(self, inputs):
+        x, anom, adj, mask, anom_pos = inputs[:5]
+        pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
+        return gat_pool(x, adj, mask, anom, anom_pos, self.gcn_layer, pooling, time_major=True)
+
     def features(self, inputs) -> torch.Tensor:
         """TimeLayer output rows [R, F] (CML: R = B; SoilNet: R = B*N) - the head's input."""
+        if self._cml_gat_time_major(inputs):
+            return self.time_layer.forward_time_major(*self._gat_time_major_input(inputs))
         if self._cml_time_major(inputs):
             x, anom, adj, mask, anom_pos = inputs[:5]
             g = self.gcn_layer
@@ -217,18 +238,22 @@ class GCNClassifier(nn.Module):
         weighted BCE and the metric accumulation (``gnnqc.ops.lstm.lstm_chain_head_tm``).
         None when the configuration is not the one those kernels implement."""
         spec = self.head_spec()
-        if spec is None or not self.per_sensor or not self._cml_time_major(inputs):
+        gat = self._cml_gat_time_major(inputs)
+        if spec is None or not self.per_sensor or not (gat or self._cml_time_major(inputs)):
             return None
         if any(d.kernel.shape[1] != 64 for d in spec[:2]) or spec[2].kernel.shape != (64, 1):
             return None
         if not (self.training is False or (self.dropout1.rate == 0 and self.dropout2.rate == 0)):
             return None
-        x, anom, adj, mask_n, anom_pos = inputs[:5]
-        g = self.gcn_layer
-        pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
-        h, M = gcn_pool(x, adj, mask_n, anom, anom_pos, g.kernel, g.bias, g.bn_gamma, g.bn_beta, g.prelu_alpha,
-                        g.bn_moving_mean, g.bn_moving_variance, self.training, g.aggregate, pooling, g.momentum,
-                        g.eps, g.dropout, time_major=True)
+        if gat:
+            h, M = self._gat_time_major_input(inputs)
+        else:
+            x, anom, adj, mask_n, anom_pos = inputs[:5]
+            g = self.gcn_layer
+            pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
+            h, M = gcn_pool(x, adj, mask_n, anom, anom_pos, g.kernel, g.bias, g.bn_gamma, g.bn_beta, g.prelu_alpha,
+                            g.bn_moving_mean, g.bn_moving_variance, self.training, g.aggregate, pooling, g.momentum,
+                            g.eps, g.dropout, time_major=True)
         if not self.time_layer.head_chain_ok(h) or spec[0].kernel.shape[0] != 128:
             # (the GCN already ran: finish on the separate-kernel path from its output)
             from ..ops.head import fused_head_loss

@@ -11,7 +11,9 @@ instead of the reference's per-(sample, step) block-diagonal SparseTensor
   HIP path (``gnnqc.ops.gcn``) is used by the CML classifier.
 * :class:`AGNNConv`, :class:`GATConv`, :class:`GatedGraphConv` (``libs/create_model.py:173-194``)
   and :class:`EdgeConv` (``xai/libs/create_model.py:147-153``): eager PyTorch,
-  chunked over time to bound the ``[B, t, N, N, .]`` edge tensors.
+  chunked over time to bound the ``[B, t, N, N, .]`` edge tensors. The CML classifier
+  runs :class:`GATConv` + node pooling through fused HIP kernels instead
+  (:func:`gnnqc.ops.gcn.gat_pool`); the layer here is their oracle and fallback.
 """
 from __future__ import annotations
 

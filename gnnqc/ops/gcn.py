@@ -422,5 +422,130 @@ def pool_nodes(h: torch.Tensor, mask: torch.Tensor, anom_pos, pooling: str = "me
     raise ValueError(pooling)
 
 
-__all__ = ["gcn_pool", "gcn_pool_hip_ok", "gcn_node_tm", "gcn_node_tm_eager", "gcn_node_tm_ok", "node_pool_weights", "masked_batchnorm", "general_conv_eager", "pool_nodes",
+# ---------------------------------------------------------------------------------------------
+# GATConv + node pooling + concat (gat.hip). ``layer`` is a :class:`gnnqc.models.graphconv.GATConv`
+# (or anything with its attributes); the eager path is the layer itself plus :func:`pool_nodes`.
+GAT_MAX_NODES = 64                      # gat.hip: one 64-bit neighbour mask per node
+GAT_WIDTHS = ((8, 16, 32), (1, 2))      # gat.hip GQ_GAT_DISPATCH: channels per head, heads
+_GAT_ACT = {None: 0, "linear": 0, "prelu": 1, "relu": 2}
+
+
+def gat_pool_weights(mask: torch.Tensor, anom_pos: torch.Tensor | None, pooling: str = "mean") -> torch.Tensor:
+    """p[b, i] such that pool_nodes(h * mask)[b, t] = sum_i p[b, i] h[b, t, i] (mask included)."""
+    m = (mask > 0).to(mask.dtype)
+    if pooling == "mean":
+        return (m / m.sum(-1, keepdim=True).clamp(min=1.0)).contiguous()
+    if pooling == "sum":
+        return m.contiguous()
+    if pooling == "selection":
+        return (F.one_hot(anom_pos.clamp(min=0), mask.shape[-1]).to(mask.dtype) * m).contiguous()
+    raise ValueError(f"linear pooling expected, got {pooling}")
+
+
+class _HipGATPool(torch.autograd.Function):
+    """Fused edge softmax -> input-space aggregation -> W, bias, activation -> node pool -> concat
+    (HIP). Launches: gat_adj_bits and gat_pool_fwd forward; gat_pool_bwd, its fixed-order record
+    sum and gat_bwd_finalize (+ gat_pool_bwd_input when dx is needed) backward. Parameter gradients
+    go straight into the optimiser's flat buffer under direct accumulation, like
+    :class:`_HipGCNPool`'s."""
+
+    @staticmethod
+    def forward(ctx, x, adj, mask, anom, pw, W, a_s, a_n, bias, alpha, act: int, Mp: int = 0, Cp: int = 0):
+        from ..utils.native import hip_ops
+        ops = hip_ops()
+        bits = ops.gat_adj_bits(adj, mask)
+        empty = x.new_zeros(0)
+        anom_t = anom.contiguous() if anom is not None else empty
+        al = alpha.contiguous() if alpha is not None else empty
+        out = ops.gat_pool_fwd(x, bits, pw, anom_t, W.contiguous(), a_s.contiguous(), a_n.contiguous(),
+                               bias.contiguous(), al, int(act), int(Mp), int(Cp))
+        ctx.tm = Mp > 0
+        ctx.act = int(act)
+        ctx.ca = 0 if anom is None else anom.shape[-1]
+        ctx.has_anom = anom is not None
+        ctx.params = (W, a_s, a_n, bias, alpha)
+        ctx.save_for_backward(x, bits, pw, W, a_s, a_n, bias, al)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from ..utils.native import hip_ops
+        from .lstm import _grad_sink
+        ops = hip_ops()
+        x, bits, pw, W, a_s, a_n, bias, al = ctx.saved_tensors
+        dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        need_p = list(need[5:10])
+        args = (W.contiguous(), a_s.contiguous(), a_n.contiguous(), bias.contiguous(), al, ctx.act, ctx.ca, ctx.tm)
+        empty = x.new_zeros(0)
+        grads = [None] * 5
+        if any(need_p):
+            tot = ops.gat_pool_bwd(x, bits, pw, dout, *args)
+            sinks = [(_grad_sink(p) if n else (empty, True)) for p, n in zip(ctx.params, need_p)]
+            ops.gat_bwd_finalize(tot, *args[:3], *[s[0] for s in sinks])
+            grads = [None if direct or not n else buf for (buf, direct), n in zip(sinks, need_p)]
+        dx = ops.gat_pool_bwd_input(x, bits, pw, dout, *args) if need[0] else None
+        danom = None
+        if ctx.has_anom and need[3]:
+            danom = dout[:, : x.shape[0], : ctx.ca].transpose(0, 1) if ctx.tm else dout[..., : ctx.ca]
+        return (dx, None, None, danom, None, *grads, None, None, None)
+
+
+def gat_pool_hip_ok(x: torch.Tensor, layer, pooling: str) -> bool:
+    """Whether :func:`gat_pool` runs the HIP kernels: on the GPU, N <= 64, Cin <= 4, linear node
+    pooling, no attention dropout while training, concatenated heads of an instantiated width and an
+    activation the kernels implement. ``GNNQC_GAT_HIP=0`` keeps the eager layer (A/B runs)."""
+    import os
+
+    from . import use_hip
+    if os.environ.get("GNNQC_GAT_HIP", "1") != "1" or x.dim() != 4 or x.dtype != torch.float32:
+        return False
+    W = layer.kernel
+    return bool(use_hip(x) and x.shape[2] <= GAT_MAX_NODES and 1 <= x.shape[-1] <= 4 and W.shape[0] == x.shape[-1]
+                and pooling in ("mean", "sum", "selection") and not (layer.dropout_rate > 0 and layer.training)
+                and layer.concat and W.shape[2] in GAT_WIDTHS[0] and W.shape[1] in GAT_WIDTHS[1]
+                and layer.activation in _GAT_ACT)
+
+
+def _time_major_pad(seq: torch.Tensor):
+    """[B, T, C] -> the time-major LSTM input [T, Mp, Cp] (Mp = B rounded up to 16, Cp to 4)."""
+    B, T, C = seq.shape
+    return F.pad(seq.transpose(0, 1), (0, (-C) % 4, 0, (-B) % 16)).contiguous()
+
+
+def gat_pool_eager(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_major: bool = False):
+    """Eager oracle of :func:`gat_pool` in its output layouts: the layer, :func:`pool_nodes` and
+    ``Concatenate([anom, pooled])``."""
+    pooled = pool_nodes(layer(x, adj, mask), mask, anom_pos, pooling)
+    out = pooled if anom is None else torch.cat([anom, pooled], dim=-1)
+    return (_time_major_pad(out), x.shape[0]) if time_major else out
+
+
+def gat_pool(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_major: bool = False):
+    """GATConv + node pooling + concat -> LSTM input ``[B, T, Ca + H*C]``; mirrors :func:`gcn_pool`.
+
+    Uses the fused HIP kernels when :func:`gat_pool_hip_ok`, otherwise the eager layer plus
+    :func:`pool_nodes`. ``time_major=True`` (HIP path only) returns ``(h [T, Mp, Cp], B)``, the
+    time-major, row- and channel-padded input of
+    :meth:`gnnqc.models.timelayer.TimeLayer.forward_time_major`, written by the kernel itself."""
+    if gat_pool_hip_ok(x, layer, pooling):
+        B = x.shape[0]
+        Mp = Cp = 0
+        if time_major:
+            Mp = (B + 15) // 16 * 16
+            Cp = layer.out_features + (anom.shape[-1] if anom is not None else 0)
+            Cp += (-Cp) % 4
+        mask_f = mask.float().contiguous()
+        pw = gat_pool_weights(mask_f, anom_pos.long() if anom_pos is not None else None, pooling)
+        out = _HipGATPool.apply(x.contiguous(), adj.float().contiguous(), mask_f, anom, pw, layer.kernel,
+                                layer.attn_kernel_self, layer.attn_kernel_neighs, layer.bias, layer.prelu_alpha,
+                                _GAT_ACT[layer.activation], Mp, Cp)
+        return (out, B) if time_major else out
+    if time_major:
+        raise ValueError("gat_pool(time_major=True) needs the HIP path")
+    return gat_pool_eager(x, adj, mask, anom, anom_pos, layer, pooling)
+
+
+__all__ = ["gat_pool", "gat_pool_eager", "gat_pool_hip_ok", "gat_pool_weights",
+           "gcn_pool", "gcn_pool_hip_ok", "gcn_node_tm", "gcn_node_tm_eager", "gcn_node_tm_ok", "node_pool_weights", "masked_batchnorm", "general_conv_eager", "pool_nodes",
            "normalized_adjacency", "prelu"]
