@@ -20,18 +20,12 @@
 // passes and writes ONE record per (workgroup, head): [dW (Cin x C) | dbias | dalpha | du_s | du_n];
 // a fixed-order column sum and gat_bwd_finalize (the u_s / u_n fold into dW, da_s, da_n) follow.
 // No float atomics anywhere: results are bitwise reproducible.
-#include "common.h"
+#include "gat_common.h"
 
 namespace gq {
 
-at::Tensor colsum(const at::Tensor& partial);     // gcn.hip
-
 constexpr int GAT_MAX_N = 64;
 constexpr int GAT_GRID_CAP = 256;        // workgroups per launch: more rows take several passes
-constexpr float GAT_SLOPE = 0.2f;        // leaky_relu slope of the attention scores
-enum { GAT_ACT_LINEAR = 0, GAT_ACT_PRELU = 1, GAT_ACT_RELU = 2 };
-
-typedef unsigned long long gat_bits_t;
 
 // bits[0][b][i]: neighbours j of node i ((adj + I * mask) > 0); bits[1][b][i]: nodes that have i
 // as a neighbour (the transposed mask, for the input gradient)
@@ -53,43 +47,6 @@ __global__ void gat_adj_bits_kernel(const float* __restrict__ adj, const float* 
   bits[e] = r;
   bits[(long)B * N + e] = c;
 }
-
-// Parameters in LDS (wave-uniform broadcast reads): W [Cin][H][C], bias [H*C], alpha [H*C],
-// u_s [Cin][H], u_n [Cin][H]
-template <int CIN, int C, int H>
-struct GatParams {
-  static constexpr int HC = H * C, NW = CIN * HC;
-  static constexpr int SIZE = NW + 2 * HC + 2 * CIN * H;
-  float* p;
-  __device__ float W(int f, int h, int c) const { return p[(f * H + h) * C + c]; }
-  __device__ float bias(int k) const { return p[NW + k]; }
-  __device__ float alpha(int k) const { return p[NW + HC + k]; }
-  __device__ float us(int f, int h) const { return p[NW + 2 * HC + f * H + h]; }
-  __device__ float un(int f, int h) const { return p[NW + 2 * HC + CIN * H + f * H + h]; }
-  __device__ void load(const float* __restrict__ Wg, const float* __restrict__ as, const float* __restrict__ an,
-                       const float* __restrict__ bg, const float* __restrict__ alg) {
-    const int tid = threadIdx.x;
-    for (int i = tid; i < NW; i += blockDim.x) p[i] = Wg[i];
-    for (int i = tid; i < HC; i += blockDim.x) {
-      p[NW + i] = bg[i];
-      p[NW + HC + i] = alg != nullptr ? alg[i] : 0.f;
-    }
-    if (tid < CIN * H) {
-      const int f = tid / H, h = tid % H;
-      float s = 0.f, n = 0.f;
-      for (int c = 0; c < C; ++c) {
-        const float w = Wg[(f * H + h) * C + c];
-        s += w * as[c * H + h];
-        n += w * an[c * H + h];
-      }
-      p[NW + 2 * HC + tid] = s;
-      p[NW + 2 * HC + CIN * H + tid] = n;
-    }
-    __syncthreads();
-  }
-};
-
-__device__ __forceinline__ float gat_leaky(float e) { return e > 0.f ? e : GAT_SLOPE * e; }
 
 // Masked edge softmax of one (node, head) and its input-space aggregate: m = max_j e_j,
 // inv = 1 / sum_j exp(e_j - m) (0 for a node without neighbours: the aggregate is then zero, as
@@ -123,17 +80,6 @@ __device__ __forceinline__ void gat_attend(gat_bits_t nb, float ss, const float 
     zc[f] *= inv;
     z[f] = den > 0.f ? xi[f] + zc[f] : 0.f;
   }
-}
-
-__device__ __forceinline__ float gat_act(float o, float al, int act) {
-  if (act == GAT_ACT_PRELU) return o > 0.f ? o : al * o;
-  if (act == GAT_ACT_RELU) return fmaxf(o, 0.f);
-  return o;
-}
-__device__ __forceinline__ float gat_act_grad(float o, float al, int act) {
-  if (act == GAT_ACT_PRELU) return o > 0.f ? 1.f : al;
-  if (act == GAT_ACT_RELU) return o > 0.f ? 1.f : 0.f;
-  return 1.f;
 }
 
 // ------------------------------------------------------------------ forward
@@ -523,31 +469,9 @@ __global__ __launch_bounds__(256) void gat_pool_bwd_input_kernel(
 }
 
 // ------------------------------------------------------------------ host
-#define GQ_GAT_DISPATCH(CIN_RT, C_RT, H_RT, ...)                                         \
-  do {                                                                                   \
-    const int key__ = (int)(CIN_RT) * 1000 + (int)(C_RT) * 10 + (int)(H_RT);             \
-    switch (key__) {                                                                     \
-      GQ_GAT_CASES(1, __VA_ARGS__) GQ_GAT_CASES(2, __VA_ARGS__)                          \
-      GQ_GAT_CASES(3, __VA_ARGS__) GQ_GAT_CASES(4, __VA_ARGS__)                          \
-      default: TORCH_CHECK(false, "gat: Cin 1..4, C in {8, 16, 32}, H in {1, 2}");       \
-    }                                                                                    \
-  } while (0)
-#define GQ_GAT_CASE(CI, CC, HH, ...) \
-  case CI * 1000 + CC * 10 + HH: { constexpr int CIN = CI, C = CC, H = HH; __VA_ARGS__; } break;
-#define GQ_GAT_CASES(CI, ...)                                                            \
-  GQ_GAT_CASE(CI, 8, 1, __VA_ARGS__) GQ_GAT_CASE(CI, 16, 1, __VA_ARGS__)                 \
-  GQ_GAT_CASE(CI, 32, 1, __VA_ARGS__) GQ_GAT_CASE(CI, 8, 2, __VA_ARGS__)                 \
-  GQ_GAT_CASE(CI, 16, 2, __VA_ARGS__) GQ_GAT_CASE(CI, 32, 2, __VA_ARGS__)
-
 struct GatDims {
   int B, T, N, Cin, C, H, NP, rpw;
 };
-
-static int gat_pow2(int n) {
-  int p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
 
 // shapes shared by the three kernels: x [B,T,N,Cin], bits [2,B,N], pw [B,N], W [Cin,H,C],
 // a_s / a_n [C,H(,1)], bias [H*C], alpha [H*C] or empty

@@ -122,6 +122,14 @@ TORCH_LIBRARY(gnnqc, m) {
         "Tensor(c!) da_n, Tensor(d!) dbias, Tensor(e!) dalpha) -> ()");
   m.def("gat_pool_bwd_input(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor W, Tensor a_s, Tensor a_n, "
         "Tensor bias, Tensor alpha, int act, int c_off, bool time_major=False) -> Tensor");
+  // fused per-node GATConv writing the time-major LSTM input (gat_node.hip)
+  m.def("gat_node_adj_bits(Tensor adj, Tensor mask) -> Tensor");
+  m.def("gat_node_fwd(Tensor x, Tensor bits, Tensor mask, Tensor W, Tensor a_s, Tensor a_n, Tensor bias, "
+        "Tensor alpha, int act, int Mp, int Cp) -> Tensor");
+  m.def("gat_node_bwd(Tensor x, Tensor bits, Tensor mask, Tensor dout, Tensor W, Tensor a_s, Tensor a_n, "
+        "Tensor bias, Tensor alpha, int act) -> Tensor");
+  m.def("gat_node_bwd_input(Tensor x, Tensor bits, Tensor mask, Tensor dout, Tensor W, Tensor a_s, Tensor a_n, "
+        "Tensor bias, Tensor alpha, int act) -> Tensor");
   // Conv1D + LeakyReLU (+ GAP) implicit GEMM (conv1d.hip)
   m.def("conv1d_fwd(Tensor x, Tensor W, Tensor b, float alpha, bool gap, bool store_y) -> Tensor[]");
   m.def("conv1d_bwd(Tensor dy, Tensor y, Tensor x, Tensor W, float alpha, bool gap, Tensor(a!) dW, "

@@ -25,8 +25,8 @@ import torch
 import torch.nn as nn
 
 from ..config import freq_minutes
-from ..ops.gcn import (gat_pool, gat_pool_hip_ok, gcn_node_tm, gcn_node_tm_ok, gcn_pool, gcn_pool_from_store,
-                       gcn_pool_hip_ok, pool_nodes, store_gcn_ok)
+from ..ops.gcn import (gat_node_tm, gat_node_tm_ok, gat_pool, gat_pool_hip_ok, gcn_node_tm, gcn_node_tm_ok, gcn_pool,
+                       gcn_pool_from_store, gcn_pool_hip_ok, pool_nodes, store_gcn_ok)
 from .graphconv import GATConv, GeneralConv, make_graph_layer
 from .layers import Dense, Dropout, LeakyReLU
 from .spatial import SensorsTimeLayer, SpatialTransformer
@@ -168,6 +168,16 @@ class GCNClassifier(nn.Module):
         return (gcn_node_tm_ok(x, g.kernel, g.aggregate, g.dropout, self.training)
                 and self.time_layer.time_major_ok(x, g.out_features + x.shape[-1]))
 
+    def _soil_gat_fused(self, inputs) -> bool:
+        """SoilNet GATConv fast path: the fused per-node GAT kernel writes the time-major LSTM input."""
+        if self.per_sensor or not isinstance(self.gcn_layer, GATConv):
+            return False
+        if self.sensors_time_layer is not None or self.spatial_transformer is not None:
+            return False
+        x = inputs[0]
+        return (gat_node_tm_ok(x, self.gcn_layer)
+                and self.time_layer.time_major_ok(x, self.gcn_layer.out_features + x.shape[-1]))
+
     def head(self, ts: torch.Tensor) -> torch.Tensor:
         d = self.dropout1(ts)
         d = self.leakyrelu4(self.dense(d))
@@ -221,6 +231,9 @@ class GCNClassifier(nn.Module):
             h, M = gcn_node_tm(x, adj, mask, g.kernel, g.bias, g.bn_gamma, g.bn_beta, g.prelu_alpha,
                                g.bn_moving_mean, g.bn_moving_variance, self.training, g.aggregate, g.momentum, g.eps)
             return self.time_layer.forward_time_major(h, M)
+        if self._soil_gat_fused(inputs):
+            x, adj, mask = inputs[:3]
+            return self.time_layer.forward_time_major(*gat_node_tm(x, adj, mask, self.gcn_layer))
         return self.time_layer(self.temporal_input(inputs))
 
     def head_spec(self):

@@ -13,7 +13,8 @@ instead of the reference's per-(sample, step) block-diagonal SparseTensor
   and :class:`EdgeConv` (``xai/libs/create_model.py:147-153``): eager PyTorch,
   chunked over time to bound the ``[B, t, N, N, .]`` edge tensors. The CML classifier
   runs :class:`GATConv` + node pooling through fused HIP kernels instead
-  (:func:`gnnqc.ops.gcn.gat_pool`); the layer here is their oracle and fallback.
+  (:func:`gnnqc.ops.gcn.gat_pool`), the network-wide SoilNet classifier per node
+  (:func:`gnnqc.ops.gcn.gat_node_tm`); the layer here is their oracle and fallback.
 """
 from __future__ import annotations
 

@@ -546,6 +546,105 @@ def gat_pool(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_ma
     return gat_pool_eager(x, adj, mask, anom, anom_pos, layer, pooling)
 
 
+# ---------------------------------------------------------------------------------------------
+# GATConv per node -> time-major LSTM input (gat_node.hip): the network-wide SoilNet front end.
+GAT_NODE_MAX_NODES = 256                # gat_node.hip: up to four 64-bit neighbour mask words per node
+
+
+class _HipGATNodeTM(torch.autograd.Function):
+    """Fused edge softmax -> input-space aggregation -> W, bias, activation -> mask, written per node
+    as the time-major LSTM input ``[T, Mp, Cp]`` (``gat_node.hip``). Launches: gat_node_adj_bits and
+    gat_node_fwd forward; gat_node_bwd, its fixed-order record sum and gat_bwd_finalize (+
+    gat_node_bwd_input when dx is needed, e.g. integrated gradients) backward. Parameter gradients
+    go straight into the optimiser's flat buffer under direct accumulation, like
+    :class:`_HipGATPool`'s."""
+
+    @staticmethod
+    def forward(ctx, x, adj, mask, W, a_s, a_n, bias, alpha, act: int, Mp: int, Cp: int):
+        from ..utils.native import hip_ops
+        ops = hip_ops()
+        bits = ops.gat_node_adj_bits(adj, mask)
+        al = alpha.contiguous() if alpha is not None else x.new_zeros(0)
+        out = ops.gat_node_fwd(x, bits, mask, W.contiguous(), a_s.contiguous(), a_n.contiguous(), bias.contiguous(),
+                               al, int(act), int(Mp), int(Cp))
+        ctx.act = int(act)
+        ctx.params = (W, a_s, a_n, bias, alpha)
+        ctx.save_for_backward(x, bits, mask, W, a_s, a_n, bias, al)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from ..utils.native import hip_ops
+        from .lstm import _grad_sink
+        ops = hip_ops()
+        x, bits, mask, W, a_s, a_n, bias, al = ctx.saved_tensors
+        dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        need_p = list(need[3:8])
+        args = (W.contiguous(), a_s.contiguous(), a_n.contiguous(), bias.contiguous(), al, ctx.act)
+        empty = x.new_zeros(0)
+        grads = [None] * 5
+        if any(need_p):
+            tot = ops.gat_node_bwd(x, bits, mask, dout, *args)
+            sinks = [(_grad_sink(p) if n else (empty, True)) for p, n in zip(ctx.params, need_p)]
+            ops.gat_bwd_finalize(tot, *args[:3], *[s[0] for s in sinks])
+            grads = [None if direct or not n else buf for (buf, direct), n in zip(sinks, need_p)]
+        dx = ops.gat_node_bwd_input(x, bits, mask, dout, *args) if need[0] else None
+        return (dx, None, None, *grads, None, None, None)
+
+
+def gat_node_tm_ok(x: torch.Tensor, layer) -> bool:
+    """Whether :func:`gat_node_tm` runs for this input: a float32 GPU tensor ``[B, T, N, Cin]`` with
+    N <= 256 and Cin <= 4, concatenated heads of an instantiated width, an activation the kernels
+    implement and no attention dropout while training. ``GNNQC_GAT_HIP=0`` keeps the eager layer
+    (A/B runs)."""
+    import os
+
+    from . import use_hip
+    if os.environ.get("GNNQC_GAT_HIP", "1") != "1" or x.dim() != 4 or x.dtype != torch.float32:
+        return False
+    W = layer.kernel
+    return bool(use_hip(x) and 1 <= x.shape[2] <= GAT_NODE_MAX_NODES and 1 <= x.shape[-1] <= 4
+                and W.shape[0] == x.shape[-1] and not (layer.dropout_rate > 0 and layer.training)
+                and layer.concat and W.shape[2] in GAT_WIDTHS[0] and W.shape[1] in GAT_WIDTHS[1]
+                and layer.activation in _GAT_ACT)
+
+
+def gat_node_tm(x, adj, mask, layer, cpad_to: int = 4):
+    """SoilNet GATConv + ``Concatenate([gat, x])`` + ``graph_reshape`` as ONE time-major tensor;
+    mirrors :func:`gcn_node_tm`.
+
+    Returns ``(h [T, Mp, Cp], M)`` with row ``m = b*N + i``, channels ``[H*C gat | Cin raw | 0 pad]``
+    (Cp a multiple of ``cpad_to``, itself a multiple of 4) and zero rows past ``M = B*N`` - the input
+    layout of :meth:`gnnqc.models.timelayer.TimeLayer.forward_time_major`. HIP path only: raises
+    when :func:`gat_node_tm_ok` does not hold."""
+    if not gat_node_tm_ok(x, layer):
+        raise ValueError("gat_node_tm needs the HIP path (see gat_node_tm_ok)")
+    if cpad_to % 4:
+        raise ValueError("gat_node_tm: cpad_to must be a multiple of 4")
+    B, T, N, Cin = x.shape
+    M = B * N
+    Mp = (M + 15) // 16 * 16
+    Cp = layer.out_features + Cin
+    Cp += (-Cp) % cpad_to
+    h = _HipGATNodeTM.apply(x.contiguous(), adj.float().contiguous(), mask.float().contiguous(), layer.kernel,
+                            layer.attn_kernel_self, layer.attn_kernel_neighs, layer.bias, layer.prelu_alpha,
+                            _GAT_ACT[layer.activation], Mp, Cp)
+    return h, M
+
+
+def gat_node_tm_eager(x, adj, mask, layer, cpad_to: int = 4):
+    """Eager oracle of :func:`gat_node_tm` (same output layout): the layer, ``cat([h, x])``, permute
+    and pad."""
+    B, T, N, Cin = x.shape
+    M = B * N
+    Mp = (M + 15) // 16 * 16
+    seq = torch.cat([layer(x, adj, mask), x], -1).permute(1, 0, 2, 3).reshape(T, M, -1)
+    C = seq.shape[-1]
+    return F.pad(seq, (0, (-C) % cpad_to, 0, Mp - M)), M
+
+
 __all__ = ["gat_pool", "gat_pool_eager", "gat_pool_hip_ok", "gat_pool_weights",
+           "gat_node_tm", "gat_node_tm_eager", "gat_node_tm_ok",
            "gcn_pool", "gcn_pool_hip_ok", "gcn_node_tm", "gcn_node_tm_eager", "gcn_node_tm_ok", "node_pool_weights", "masked_batchnorm", "general_conv_eager", "pool_nodes",
            "normalized_adjacency", "prelu"]
