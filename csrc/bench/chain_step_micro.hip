@@ -1,6 +1,6 @@
 // Microbenchmark of the chain kernels' serial LSTM step (H = 16, one 16-sequence tile per
 // workgroup, 4 compute waves, one cell per lane): shader cycles per step for variants that add
-// the pieces of lstm_chain.hip's step loop one at a time, to find what sets the ~800-cycle step.
+// the pieces of lstm_chain_fwd.hip's step loop one at a time, to find what sets the ~800-cycle step.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 csrc/bench/chain_step_micro.hip -o build/chain_step_micro
 //   build/chain_step_micro            -> one JSON line per variant

@@ -76,7 +76,7 @@ __global__ void nonfinite_kernel(const float* __restrict__ x, long n, int* out) 
 // publishes ok = (count == 0) in state[2], advances the optimiser step counter only for
 // a good step, counts skipped steps in state[3] and re-arms state[0..1] for the next
 // launch. The Adam kernel then reads state[2]. No host synchronisation anywhere.
-// ext (optional): the LSTM chain kernels' control words (lstm_chain.hip). ext[2] is set when a
+// ext (optional): the LSTM chain kernels' control words (lstm_chain_ctl.hip). ext[2] is set when a
 // chain consumer's bounded spin timed out in this step - its activations / gradients then came
 // from stale data, so the step is rejected like a non-finite one; the flag is cleared and
 // counted in ext[3] (the host raises on it at epoch end).

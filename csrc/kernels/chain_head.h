@@ -57,6 +57,15 @@ struct ChainHead {
   float* gpart;                               // [ntiles][ChainHeadRec::PITCH] weight-gradient records
   float *dW1, *db1, *dW2, *db2, *dW3, *db3;   // accumulated (+=): .grad views or zeroed sinks
 };
+// time4_head.hip fills it for its own launches and for the chain's (lstm_chain_fwd.hip, lstm_chain_bwd.hip):
+// the forward head arguments (weights, labels, metric accumulators, ticket) ...
+void t4_head_fwd_args(ChainHead& hd, at::TensorList head, const at::Tensor& y, const at::Tensor& mask, int64_t M,
+                      int Mp, double alpha1, double alpha2, double w0, double w1, const at::Tensor& sums,
+                      const at::Tensor& hist, at::Tensor& logits, at::Tensor& loss, at::Tensor& part);
+// ... and the backward ones (weights, labels, dloss, gradient sinks, tickets)
+void t4_head_bwd_args(ChainHead& hd, at::TensorList head, const at::Tensor& y, const at::Tensor& mask, int64_t M,
+                      int Mp, double alpha1, double alpha2, double w0, double w1, const at::Tensor& dloss,
+                      at::TensorList hgrads, at::Tensor& gpart);
 
 // gradient record of one tile: dW1 [F*64] | db1 [64] | dW2 [64*64] | db2 [64] | dW3 [64] | db3 [1]
 template <int F>

@@ -1,4 +1,4 @@
-// Weight-gradient epilogue of the backward chain's upper workgroups (lstm_chain.hip): after its reverse loop the
+// Weight-gradient epilogue of the backward chain's upper workgroups (lstm_chain_bwd.hip): after its reverse loop the
 // workgroup of (layer, tile) - an H = 32 / 64 chain stage or time4 - builds the dW | db and dU partial of its
 // own 16 sequences over all T steps of the layer and writes it as ONE split record in GradsGeom's layout
 // (lstm_grads_body.h), record index = tile. The layer's reduction (lstm_grads_reduce_multi_kernel) then runs

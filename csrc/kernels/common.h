@@ -79,7 +79,7 @@ struct DeferredRed {
 std::vector<DeferredRed>& deferred_reds();      // lstm_grads.hip
 
 // host functions of one kernel file that others call
-int* chain_ctl(int dev);   // lstm_chain.hip: the device's chain control words ([4] / [5] head tickets, [7] a gradient
+int* chain_ctl(int dev);   // lstm_chain_ctl.hip: the device's chain control words ([4] / [5] head tickets, [7] a gradient
                            // producer saw a non-finite value)
 at::Tensor maxpool1d_bwd(const at::Tensor& dy, const at::Tensor& idx, int64_t T, int64_t p);   // pool.hip
 

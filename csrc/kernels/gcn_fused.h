@@ -139,7 +139,7 @@ struct GcnCoefFwdLds {
 };
 
 // ---- the whole training-step forward as PRODUCER workgroups of the LSTM chain forward launch
-// (lstm_chain.hip): one workgroup (blockDim.x threads, a multiple of 256, F / 4 threads per row) per
+// (lstm_chain_fwd.hip): one workgroup (blockDim.x threads, a multiple of 256, F / 4 threads per row) per
 // sample row b of [0, Mp), all T steps. The arithmetic of gcn_fused_fwd_kernel (the batch's moment
 // records summed in one fixed order - the same in every workgroup -, the BatchNorm prep, the
 // node-pooled PReLU output, the flagged series) plus, when coef != nullptr, the backward

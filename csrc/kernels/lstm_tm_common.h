@@ -1,5 +1,5 @@
 // Pieces shared by the time-major LSTM kernels (lstm_tm_fwd.hip, lstm_tm_bwd.hip, lstm_grads_jobs.hip,
-// lstm_chain.hip, time4_head.hip): tile constants, streamers, the fused pool, and the host side's shape
+// lstm_chain_fwd.hip, lstm_chain_bwd.hip, time4_head.hip): tile constants, streamers, the fused pool, and the host side's shape
 // predicates with the dispatcher that turns a launch's run-time shape into template arguments.
 #pragma once
 #include "common.h"
@@ -170,7 +170,7 @@ struct GranuleH {
 };
 
 // ---- fused MaxPooling1D(P) (valid, stride P) of a stored h sequence (the chain forward's last
-// stage, lstm_chain.hip, whose pooled output leaves the chain). Each storer lane owns
+// stage, lstm_chain_fwd.hip, whose pooled output leaves the chain). Each storer lane owns
 // one float4 granule of the [16][H] tile for the whole sequence, so the running max and the
 // byte argmax (first maximum wins, like TF's MaxPoolGrad) stay in its registers; the pooled
 // granule and its 4 argmax bytes are written when a window closes. Layout = maxpool1d_fwd's

@@ -2,7 +2,7 @@
 // head and the weighted BCE, forward and backward, for gfx950 (libs/create_model.py:61-79 time4,
 // :204-239 head; loss libs/fit_model.py:76-111).
 //
-// After the six pipelined layers (lstm_chain.hip) the CML step used to run time4 and the head as
+// After the six pipelined layers (lstm_chain_fwd.hip) the CML step used to run time4 and the head as
 // five launches (lstm_fwd<128>, head_fwd, head_bwd, lstm_bwd<128>, lstm_dx: ~82 us, latency only,
 // plus pad / transpose copies between them). Here: ONE forward kernel (time4's six steps, then
 // the head, the loss and the metric accumulation as the epilogue) and ONE backward kernel (the
@@ -591,7 +591,7 @@ static void t4_check(const at::Tensor& x, const at::Tensor& W, const at::Tensor&
 
 // The forward head's arguments: weights, labels, outputs (logits [M], loss [1], per-tile partials
 // allocated here), the metric accumulators (sums [6] fp64 / hist [2, bins], empty: none) and the
-// arrival ticket (chain control word 4). Also used by lstm_chain_head_fwd (lstm_chain.hip).
+// arrival ticket (chain control word 4). Also used by lstm_chain_head_fwd (lstm_chain_fwd.hip; declared in chain_head.h).
 void t4_head_fwd_args(ChainHead& hd, at::TensorList head, const at::Tensor& y, const at::Tensor& mask, int64_t M,
                       int Mp, double alpha1, double alpha2, double w0, double w1, const at::Tensor& sums,
                       const at::Tensor& hist, at::Tensor& logits, at::Tensor& loss, at::Tensor& part) {
@@ -667,7 +667,7 @@ std::vector<at::Tensor> time4_head_fwd(const at::Tensor& x, const at::Tensor& W,
 
 // The backward head's arguments: dloss [1], the head gradient sinks (accumulated), the per-tile
 // record buffer (allocated here) and the chain control words' tickets ([5] arrivals, [8] reduce
-// done; [7] is the non-finite gradient flag). Also used by lstm_chain_head_bwd (lstm_chain.hip).
+// done; [7] is the non-finite gradient flag). Also used by lstm_chain_head_bwd (lstm_chain_bwd.hip; declared in chain_head.h).
 void t4_head_bwd_args(ChainHead& hd, at::TensorList head, const at::Tensor& y, const at::Tensor& mask, int64_t M,
                       int Mp, double alpha1, double alpha2, double w0, double w1, const at::Tensor& dloss,
                       at::TensorList hgrads, at::Tensor& gpart) {

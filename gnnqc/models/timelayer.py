@@ -194,7 +194,7 @@ class TimeLayer(nn.Module):
     def _chain_plan(seq, h: torch.Tensor):
         """Leading run of time-major LSTM layers (returning sequences, each optionally followed
         by a MaxPooling1D) that the cross-CU chain kernel takes: ``(modules, pools, next index)``
-        or None. Constraints of ``lstm_chain.hip``: H in {16, 32, 64}, inputs <= 64 channels and
+        or None. Constraints of ``lstm_chain_fwd.hip``: H in {16, 32, 64}, inputs <= 64 channels and
         no wider than the layer, all workgroups co-resident (``chain_fits``)."""
         from ..ops import use_hip
         from ..ops.lstm import chain_fits

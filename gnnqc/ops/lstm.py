@@ -373,7 +373,7 @@ def _tm_layer_backward(dout, x, W, U, b, h, g, c, params, need_w, need_dx):
 
 class _HipLSTMChain(torch.autograd.Function):
     """A stack of time-major layers (with MaxPooling1D between some of them) whose forward
-    runs as ONE cross-CU pipelined kernel (``lstm_chain.hip``: every layer of a 16-sequence
+    runs as ONE cross-CU pipelined kernel (``lstm_chain_fwd.hip``: every layer of a 16-sequence
     tile on its own CU, consuming the previous layer's output as it is produced). The
     backward runs the per-layer backward kernels in reverse, un-pooling between them."""
 
@@ -465,7 +465,7 @@ class _HipLSTMChain(torch.autograd.Function):
 
 class _HipLSTMChainHead(torch.autograd.Function):
     """CML TimeLayer + classifier head + weighted BCE in two forward and two backward launches:
-    the six pipelined time-major layers as ONE chain kernel (``lstm_chain.hip``), then time4
+    the six pipelined time-major layers as ONE chain kernel (``lstm_chain_fwd.hip``), then time4
     (H = 128, last state) with the Dense head, the loss and the metric accumulation as ONE
     kernel (``time4_head.hip``); backward: the head backward + time4's reverse recurrence as ONE
     kernel, whose dx (gradient of the chain's pooled output) feeds ONE chain backward.
@@ -676,7 +676,7 @@ _CHAIN_CTL = {}
 def chain_ctl(device) -> Optional[torch.Tensor]:
     """The device's chain control words ``[epoch, finished, timeout flag, rejected steps, fwd / bwd
     head tickets, debug spin limit, non-finite gradient flag, head backward arrivals, 0 ...]`` as an
-    int32[16] view (``lstm_chain.hip``); None off the GPU. The optimiser's update reads and clears
+    int32[16] view (``lstm_chain_ctl.hip``); None off the GPU. The optimiser's update reads and clears
     the timeout / non-finite flags inside the captured step."""
     device = torch.device(device)
     if device.type != "cuda":

@@ -1,4 +1,4 @@
-"""Float64 model of the chain forward (``lstm_chain.hip``) that rounds where the kernel rounds, stage by
+"""Float64 model of the chain forward (``lstm_chain_fwd.hip``) that rounds where the kernel rounds, stage by
 stage, with everything the kernel stores: per stage h, the gates (bf16-rounded, as packed), c, the
 MaxPooling1D(3) output that feeds the next stage (or leaves the chain) and its first-maximum argmax.
 

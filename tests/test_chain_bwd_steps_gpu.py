@@ -1,4 +1,4 @@
-"""Chain backward (lstm_chain.hip) at the sequence lengths where the H = 16 stages' one-step-ahead
+"""Chain backward (lstm_chain_bwd.hip) at the sequence lengths where the H = 16 stages' one-step-ahead
 dh staging can go wrong: stages shorter than the ring, un-pooling tails, lengths that are / are not
 multiples of the ring depth, one and three row tiles.
 

@@ -1,4 +1,4 @@
-"""Chain forward (lstm_chain.hip chain_stage) at the sequence lengths where the H = 16 stages' step
+"""Chain forward (lstm_chain_fwd.hip chain_stage) at the sequence lengths where the H = 16 stages' step
 pipeline can go wrong: the publisher wave runs two steps behind the cells and drains the last two
 steps behind the loop, the H = 16 stream consumer has a ring depth of its own (D = CHAIN_D16S = 4)
 and loads a 16-channel tile class.
@@ -29,7 +29,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-D16S = 4                       # CHAIN_D16S (lstm_chain.hip)
+D16S = 4                       # CHAIN_D16S (lstm_chain_fwd.hip)
 # 3 x the parent library's largest error on these cases (profiles/chain_fwd_steps_tests.txt), <= 3e-3
 BOUND = {"h": 1.34e-3, "g": 1.31e-3, "c": 1.29e-3, "pooled": 1.31e-3}
 

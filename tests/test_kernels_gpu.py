@@ -772,7 +772,7 @@ def test_timelayer_pair_fusion_matches_unfused(cuda_device, monkeypatch):
 @pytest.mark.parametrize("bwd", ["chain", "per_layer"])
 @pytest.mark.parametrize("M", [128, 40, 300])
 def test_chain_forward_matches_per_layer(cuda_device, monkeypatch, M, bwd):
-    """CML TimeLayer: the cross-CU pipelined stack forward (lstm_chain.hip) == the per-layer
+    """CML TimeLayer: the cross-CU pipelined stack forward (lstm_chain_fwd.hip) == the per-layer
     kernels (no pair fusion) for the output and every gradient; repeated launches (fresh
     epochs over reused stream buffers) stay identical and no consumer spin timed out."""
     from gnnqc.models.timelayer import TimeLayer
