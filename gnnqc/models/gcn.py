@@ -248,7 +248,7 @@ class GCNClassifier(nn.Module):
     def fused_loss(self, inputs, y: torch.Tensor, mask: torch.Tensor, w0: float, w1: float, sums=None, hist=None):
         """(loss, logits) through the headed-chain fast path (CML, GPU): the fused GCN kernel
         writes the time-major LSTM input, then ONE kernel runs the whole TimeLayer, the head, the
-        weighted BCE and the metric accumulation (``gnnqc.ops.lstm.lstm_chain_head_tm``).
+        weighted BCE and the metric accumulation (``gnnqc.ops.lstm_chain.lstm_chain_head_tm``).
         None when the configuration is not the one those kernels implement."""
         spec = self.head_spec()
         gat = self._cml_gat_time_major(inputs)

@@ -100,8 +100,9 @@ class TimeLayer(nn.Module):
         rows past M; C may carry zero channels past the first layer's input width).
         Returns ``[M, out_features]``. Producers that can write this layout directly (the
         SoilNet GCN kernel) skip the transpose/pad copy of :meth:`_forward_tm`."""
-        from ..ops.lstm import (_chain_on, last128_eligible, lstm_chain_tm, lstm_last128_tm, lstm_layer_tm,
-                                lstm_pair_tm, pool_fusion, tm_eligible)
+        from ..ops.lstm import (last128_eligible, lstm_chain_tm, lstm_last128_tm, lstm_layer_tm, lstm_pair_tm,
+                                pool_fusion, tm_eligible)
+        from ..ops.lstm_chain import _chain_on
         from ..ops.pool import max_pool1d_tm
         if self.layer_type != "lstm":
             # CNN branch behind a time-major producer (the store-fused CML GCN front end): [M, T, Cin]
@@ -163,10 +164,11 @@ class TimeLayer(nn.Module):
 
     def head_chain_ok(self, h: torch.Tensor) -> bool:
         """Whether the whole LSTM branch of a time-major input ``h`` [T, Mp, C] runs as the chain +
-        time4/head kernels (:func:`gnnqc.ops.lstm.lstm_chain_head_tm`): every layer but the last in
+        time4/head kernels (:func:`gnnqc.ops.lstm_chain.lstm_chain_head_tm`): every layer but the last in
         the chain plan, the last one H = 128 returning its last state after <= 16 steps."""
-        from ..ops.lstm import _chain_on
-        if self.layer_type != "lstm" or not _chain_on() or os.environ.get("GNNQC_HEAD_CHAIN", "1") != "1":
+        from ..ops import switch_on
+        from ..ops.lstm_chain import _chain_on
+        if self.layer_type != "lstm" or not _chain_on() or not switch_on("GNNQC_HEAD_CHAIN"):
             return False
         seq = self._sequence()
         plan = self._chain_plan(seq, h)

@@ -20,10 +20,16 @@ import torch
 from ..utils.native import hip_available, hip_ops
 
 
+def switch_on(name: str, default: bool = True) -> bool:
+    """An on / off switch of the environment (``GNNQC_*``), read at every use: on when it is ``1``,
+    ``default`` when it is not set."""
+    return os.environ.get(name, "1" if default else "0") == "1"
+
+
 def use_hip(t: torch.Tensor) -> bool:
     if not t.is_cuda:
         return False
-    if os.environ.get("GNNQC_FORCE_EAGER", "0") == "1":
+    if switch_on("GNNQC_FORCE_EAGER", False):
         return False
     hip_ops()   # raises if the library is missing
     return True
@@ -42,7 +48,7 @@ def set_deterministic(flag: bool = True) -> bool:
 
 
 def deterministic() -> bool:
-    return os.environ.get("GNNQC_DETERMINISTIC", "0") == "1"
+    return switch_on("GNNQC_DETERMINISTIC", False)
 
 
 from .lstm import lstm_layer, lstm_eager  # noqa: E402

@@ -12,7 +12,7 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from .lstm import _grad_sink
+from .wgrad import _grad_sink
 
 
 def conv1d_act_eager(x, W, b, alpha: float, gap: bool = False):

@@ -100,7 +100,7 @@ class _HipGCNPool(torch.autograd.Function):
     Launches per training step: gcn_prep (pool weights + batch moments + BN prep) and
     gcn_pool_fwd forward; gcn_pool_bwd and gcn_bwd_finalize (+ gcn_pool_bwd_input when dx is
     needed) backward. Weight gradients go straight into the optimiser's flat buffer when
-    direct accumulation is on (see ``gnnqc.ops.lstm.direct_grad_accumulation``)."""
+    direct accumulation is on (see ``gnnqc.ops.wgrad.direct_grad_accumulation``)."""
 
     @staticmethod
     def forward(ctx, x, adj, mask, anom, anom_pos, agg_mean: bool, pool: int, W, b, gamma, beta, alpha,
@@ -124,7 +124,7 @@ class _HipGCNPool(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         from ..utils.native import hip_ops
-        from .lstm import _grad_sink
+        from .wgrad import _grad_sink
         ops = hip_ops()
         x, w, mask, W, b, alpha, st, S = ctx.saved_tensors
         dout = dout.contiguous()
@@ -212,7 +212,7 @@ class _HipGCNNodeTM(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         from ..utils.native import hip_ops
-        from .lstm import _grad_sink
+        from .wgrad import _grad_sink
         ops = hip_ops()
         x, bitsT, rs, mask, W, b, alpha, st, S = ctx.saved_tensors
         dout = dout.contiguous()
@@ -305,7 +305,7 @@ class _HipStoreGCN(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh, _dy, _dym, _dwid):
         from ..utils.native import hip_ops
-        from .lstm import _grad_sink
+        from .wgrad import _grad_sink
         W, b, alpha, S, st, cf = ctx.saved_tensors
         need = ctx.needs_input_grad[2:7]
         if dh is None or not any(need):
@@ -313,7 +313,7 @@ class _HipStoreGCN(torch.autograd.Function):
         if not ctx.training:
             raise RuntimeError("gcn_fused backward: parameter gradients in eval mode take the generic path")
         sinks = [(_grad_sink(p) if n else (torch.zeros_like(p), False)) for p, n in zip(ctx.params, need)]
-        from .lstm import defer_to_grads_launch
+        from .wgrad import defer_to_grads_launch
         direct = all(direct for (_, direct), n in zip(sinks, need) if n)
         if cf.numel() > 0:
             # coefficient form: dh x coef, deferred onto the batched LSTM weight-gradient launch when
@@ -470,7 +470,7 @@ class _HipGATPool(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         from ..utils.native import hip_ops
-        from .lstm import _grad_sink
+        from .wgrad import _grad_sink
         ops = hip_ops()
         x, bits, pw, W, a_s, a_n, bias, al = ctx.saved_tensors
         dout = dout.contiguous()
@@ -575,7 +575,7 @@ class _HipGATNodeTM(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         from ..utils.native import hip_ops
-        from .lstm import _grad_sink
+        from .wgrad import _grad_sink
         ops = hip_ops()
         x, bits, mask, W, a_s, a_n, bias, al = ctx.saved_tensors
         dout = dout.contiguous()

@@ -6,7 +6,7 @@ the class-weighted, SUM_OVER_BATCH_SIZE binary cross-entropy of
 forward kernel (which also adds the step's loss sum, confusion counts and score
 histogram into the device metric accumulators) and one backward kernel that
 writes every head gradient straight into the optimiser's flat gradient buffer
-(:func:`gnnqc.ops.lstm.direct_grad_accumulation`). Elsewhere it is plain PyTorch.
+(:func:`gnnqc.ops.wgrad.direct_grad_accumulation`). Elsewhere it is plain PyTorch.
 """
 from __future__ import annotations
 
@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 import torch
 import torch.nn.functional as F
 
-from .lstm import _grad_sink
+from .wgrad import _grad_sink
 
 
 def head_eager(feat, W1, b1, W2, b2, W3, b3, alpha1: float, alpha2: float) -> torch.Tensor:

@@ -1,7 +1,7 @@
 """Reference LSTM with the HIP kernels' rounding points, for numerics tests.
 
 The recurrences run on bf16 MFMA (``lstm_chain_fwd.hip`` / ``lstm_chain_bwd.hip``, ``lstm_tm_fwd.hip`` / ``lstm_tm_bwd.hip``, ``time4_head.hip``,
-``lstm_grads.hip``), so comparing them with a plain float64 model needs tolerances of several
+``lstm_grads.hip``; their operators are ``gnnqc/ops/lstm.py`` and ``gnnqc/ops/lstm_chain.py``), so comparing them with a plain float64 model needs tolerances of several
 percent (bf16 has 8 significand bits), loose enough to hide a real bug. This reference keeps
 float64 arithmetic everywhere EXCEPT where the kernels round, and rounds there exactly like
 them (round-to-nearest-even to bf16):

@@ -15,7 +15,7 @@ a second one. Consequences on MI355X:
   counted in ``skipped_steps``. It lives inside the captured graph, so it costs no
   host synchronisation. In DP the all-reduce spreads a NaN to every rank, so all
   ranks skip the same step. The same guard rejects a step in which an LSTM chain kernel's
-  bounded spin timed out (``gnnqc.ops.lstm.check_chain`` raises on it at epoch end).
+  bounded spin timed out (``gnnqc.ops.lstm_chain.check_chain`` raises on it at epoch end).
 
 Optimisers by name like ``libs/fit_model.py:71-74``: adam (Keras eps 1e-7,
 "epsilon-hat" update), sgd, rmsprop (Keras defaults rho .9, eps 1e-7).

@@ -1,9 +1,9 @@
 """Training / evaluation engine: device-resident, HIP-graph captured steps.
 
 One training step = gather batch from HBM by window id -> forward -> weighted BCE
--> backward into the flat gradient buffer -> (DP) one RCCL all-reduce -> one Adam
-kernel. On GPU the gather+forward+backward(+optimizer when world == 1) is
-captured once into a HIP graph (``torch.cuda.CUDAGraph``) and replayed with new
+-> backward into the flat gradient buffer (``gnnqc.ops.wgrad``: direct accumulation and the
+weight-gradient queue) -> (DP) one RCCL all-reduce -> one Adam kernel. On GPU the
+gather+forward+backward(+optimizer when world == 1) is captured once into a HIP graph (``torch.cuda.CUDAGraph``) and replayed with new
 window ids, so a step costs a handful of host calls regardless of the ~100 kernels
 inside. Metric accumulators (loss sums, confusion counts, score histograms) live
 on the device and are only read at epoch end - no host sync per step.

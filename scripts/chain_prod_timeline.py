@@ -18,7 +18,7 @@ def main():
     from gnnqc.data.store import DeviceStore
     from gnnqc.data.synthetic import make_cml_raw
     from gnnqc.models import GCNClassifier
-    import gnnqc.ops.lstm as L
+    import gnnqc.ops.lstm_chain as L
     from gnnqc.ops.optim import make_optimizer
     from gnnqc.train.engine import Trainer
     from gnnqc.train.loss import calculate_weights

@@ -253,7 +253,7 @@ def test_trainer_step_with_and_without_chain_records(cuda_device, monkeypatch):
     from gnnqc.data.store import DeviceStore
     from gnnqc.data.synthetic import make_cml_raw
     from gnnqc.models import GCNClassifier
-    from gnnqc.ops import lstm as L
+    from gnnqc.ops import lstm_chain as L
     from gnnqc.ops.optim import make_optimizer
     from gnnqc.train.engine import Trainer
     lr = 1e-3

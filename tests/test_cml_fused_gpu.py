@@ -223,3 +223,39 @@ def test_head_backward_precomputed_by_forward_launch(cuda_device, cml_windows, m
         err = (h1[n] - h0[n]).norm().item()
         assert err <= 1e-4 * (h0[n].norm().item() + 1e-9), (n, err, h0[n].norm().item())
         assert abs(h0[n].norm().item() - 2.5 * g0[n].norm().item()) <= 1e-2 * h0[n].norm().item() + 1e-9, n
+
+
+def test_frozen_chain_layer_takes_no_gradient_sink(cuda_device, cml_windows):
+    """A chain layer whose weights are frozen and have no ``.grad`` buffer (here the second H = 16 layer)
+    gets no gradient sink in the headed chain's backward: no zero buffers are made for it, the count
+    of unflagged gradient writes (which sends the trainer to the scanning Adam) stays, the frozen
+    parameters keep ``grad = None``, and every other gradient is that of the run with nothing frozen
+    (by norm, not bitwise: the tail launch has one job fewer, its split layout may differ). B = 32:
+    two 16-sequence tiles per stage."""
+    from gnnqc.ops.lstm import direct_grad_accumulation, unflagged_grad_writes
+    _, _, _, model, b = _setup(cuda_device, cml_windows, B=32)
+    inputs = b.model_inputs("cml")
+    _, _, ref = _grads(model, lambda: model.fused_loss(inputs, b.y, b.y_mask, 1.0, 5.0))
+    layer = model.time_layer.time2
+    assert layer.units == 16
+    frozen = [layer.kernel, layer.recurrent_kernel, layer.bias]
+    for p in model.parameters():
+        p.grad = torch.zeros_like(p)
+    for p in frozen:
+        p.requires_grad_(False)
+        p.grad = None
+    before = unflagged_grad_writes()
+    with direct_grad_accumulation(True):
+        loss, _ = model.fused_loss(inputs, b.y, b.y_mask, 1.0, 5.0)
+        loss.backward(torch.ones((), device=loss.device))
+    torch.cuda.synchronize()
+    assert unflagged_grad_writes() == before
+    assert all(p.grad is None for p in frozen)
+    compared = 0
+    for n, p in model.named_parameters():
+        if any(p is f for f in frozen):
+            continue
+        err, scale = (p.grad - ref[n]).norm().item(), ref[n].norm().item()
+        assert err <= 5e-3 * scale, (n, err, scale)
+        compared += 1
+    assert compared == len(ref) - 3

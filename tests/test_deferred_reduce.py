@@ -11,7 +11,7 @@ LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="HIP extension not built")
 def test_deferred_reduce_switch_scoped_to_direct_accumulation():
     import torch
-    from gnnqc.ops import lstm as L
+    from gnnqc.ops import wgrad as L
     torch.ops.load_library(LIB)
     ops = torch.ops.gnnqc
     assert ops.lstm_defer_reduce(False) is False
@@ -32,7 +32,7 @@ def test_deferred_reduce_switch_scoped_to_direct_accumulation():
 
 
 def test_deferred_reduce_kill_switch(monkeypatch):
-    from gnnqc.ops import lstm as L
+    from gnnqc.ops import wgrad as L
     monkeypatch.setenv("GNNQC_DEFER_REDUCE", "0")
     with L.direct_grad_accumulation(True):
         with L._deferred_reduce(True):

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 def test_deferred_reduce_matches_per_layer(cuda_device, monkeypatch):
     from gnnqc.models.timelayer import TimeLayer
-    from gnnqc.ops import lstm as L
+    from gnnqc.ops import wgrad as L
     monkeypatch.setenv("GNNQC_CHAIN", "0")          # the per-layer kernels, as on the SoilNet step
     torch.manual_seed(0)
     tl = TimeLayer(20, 16, 2).to(cuda_device)

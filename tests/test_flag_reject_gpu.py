@@ -28,7 +28,7 @@ def test_nan_in_one_producer_rejects_whole_step(case, cuda_device, cml_windows, 
     from gnnqc.ops.optim import make_optimizer
     from gnnqc.train.engine import Trainer
     env, pred = CASES[case]
-    import gnnqc.ops.lstm as L
+    import gnnqc.ops.wgrad as L
     for k, v in env.items():
         if k == "pipe":
             monkeypatch.setattr(L._Pipe, "enabled", v)       # per-layer fused backward + lstm_grads reduce

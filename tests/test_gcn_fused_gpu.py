@@ -177,8 +177,8 @@ def test_gcn_backward_inside_grads_launch_matches_own_launch(cuda_device, cml_wi
     (GNNQC_GCN_DEFER=1, the training default) == its own launch: every parameter gradient of a full
     CML loss backward (float atomics: equal up to summation order)."""
     from gnnqc.data.store import CursorIds
-    from gnnqc.ops import lstm as L
-    from gnnqc.ops.lstm import direct_grad_accumulation
+    from gnnqc.ops import wgrad as L
+    from gnnqc.ops.wgrad import direct_grad_accumulation
     _, st, model = _setup(cuda_device, cml_windows)
     ids = _ids(st, 128, cuda_device)
     assert model.store_fused_ok(st)

@@ -398,8 +398,9 @@ def test_lstm_tm_recomputed_gates_match_saved_gates(cuda_device, monkeypatch, H,
     within bf16-gate rounding of each other, and the RG gradients against an fp64 eager oracle.
     (Sharp bounds against the rounding-aware oracle, per branch: tests/test_lstm_tm_kernels_gpu.py.)"""
     from gnnqc.ops import lstm as L
+    from gnnqc.ops.wgrad import _Pipe
     from gnnqc.utils.native import hip_ops
-    monkeypatch.setattr(L._Pipe, "enabled", False)      # (training layers of any size take RG)
+    monkeypatch.setattr(_Pipe, "enabled", False)     # (training layers of any size take RG)
     dev = cuda_device
     gen = torch.Generator().manual_seed(7 * H + Din + 100 * wgrad + 1000 * pair)
     M, T, Mp = 72, 37, 80
@@ -885,7 +886,7 @@ def test_pipe_training_steps_match_fused(cuda_device, cml_windows, monkeypatch, 
     from gnnqc import config as C
     from gnnqc.data.store import DeviceLoader, DeviceStore
     from gnnqc.models import GCNClassifier
-    from gnnqc.ops.lstm import _Pipe
+    from gnnqc.ops.wgrad import _Pipe
     from gnnqc.ops.optim import make_optimizer
     from gnnqc.train.engine import Trainer
     pc, ws = cml_windows
@@ -918,7 +919,7 @@ def test_pipe_lstm_backward_gradients(cuda_device, cml_windows, monkeypatch, ds)
     from gnnqc import config as C
     from gnnqc.data.store import DeviceStore
     from gnnqc.models import GCNClassifier
-    from gnnqc.ops.lstm import _Pipe, direct_grad_accumulation
+    from gnnqc.ops.wgrad import _Pipe, direct_grad_accumulation
     pc, ws = cml_windows if ds == "cml" else _soil_small_windows()
     st = DeviceStore(ws, "rolling_median" if ds == "cml" else "scale_range", pc.graph, device=cuda_device)
     torch.manual_seed(0)
