@@ -292,7 +292,9 @@ __device__ __forceinline__ void chain_bwd_stage16(const ChainBStage S, int tile,
     const int nx = 16 * Din;
     const size_t xstep = (size_t)Mp * Din;
     // publisher wave pj of NPUB publishes the 64-element slices pj, pj + NPUB, ... of each dx tile
-    const int pj = (tid - NT) >> 6;
+    // (pj as a scalar: derived from tid alone, the element counts below were per-lane values to the
+    // compiler and every "wave-uniform" test in the step an exec-masked branch)
+    const int pj = __builtin_amdgcn_readfirstlane((tid - NT) >> 6);
     constexpr int ESTR = 64 * NPUB;
     const int dq = ESTR / Din, dr = ESTR % Din;
     // LDS reads of CHAINB_PUBBATCH elements per lane first, then their stores: a read -> wait -> store
@@ -300,28 +302,40 @@ __device__ __forceinline__ void chain_bwd_stage16(const ChainBStage S, int tile,
     // Din / 4 elements per lane, the same count on every lane since Din % 4 == 0). (All Din / 4 at
     // once, up to 16, pushed the kernel from 32 to 176 bytes of scratch: chain bwd 133 -> 258 us.)
     constexpr int PUBN = CHAINB_PUBBATCH > 0 ? CHAINB_PUBBATCH : 1;   // elements per lane per batch
+    // The publisher's step paces the stage (profiles/chain_bwd_step_micro.txt: 951 shader clocks per step,
+    // 779 with idle publishers, 843 with this form), so nothing that is fixed for the launch stays in it.
+    // A lane's elements 64 pj + lane + ESTR i, i < npub, sit at fixed offsets of a dxs buffer: the
+    // division by Din is done once, here. PUBE: a lane's elements of the widest tile (Din <= 64: chain_bwd_setup).
+    constexpr int PUBE = (16 * 64 + ESTR - 1) / ESTR;
+    const int npub = min(max((nx - 64 * pj + ESTR - 1) / ESTR, 0), PUBE);   // wave-uniform: nx % 64 == 0
+    int lofs[PUBE];
+    {
+      int row = (lane + 64 * pj) / Din, k = (lane + 64 * pj) % Din;
+#pragma unroll
+      for (int i = 0; i < PUBE; ++i) {
+        lofs[i] = row * (32 * KX + CHAINB_XPAD) + k;
+        row += dq;
+        k += dr;
+        if (k >= Din) { k -= Din; ++row; }
+      }
+    }
+    const size_t o0 = (size_t)row0 * Din + 64 * pj + lane;
     auto publish = [&](int buf, int ts) {
       const unsigned tag = tagb | (unsigned)ts;
-      for (int e0 = 64 * pj; e0 < nx; e0 += ESTR * PUBN) {
-        const int niter = min((nx - e0 + ESTR - 1) / ESTR, PUBN);
-        float vv[PUBN];
-        int row = (lane + e0) / Din, k = (lane + e0) % Din;
+      const float* xt = &dxs[buf][0][0];
+      const size_t o = o0 + (size_t)ts * xstep;
 #pragma unroll
-        for (int i = 0; i < PUBN; ++i) {
-          if (i < niter) {                          // wave-uniform
-            vv[i] = dxs[buf][row][k];
-          }
-          row += dq;
-          k += dr;
-          if (k >= Din) { k -= Din; ++row; }
+      for (int i0 = 0; i0 < PUBE; i0 += PUBN) {
+        float vv[PUBN];
+#pragma unroll
+        for (int i = i0; i < i0 + PUBN && i < PUBE; ++i) {
+          if (i < npub) vv[i - i0] = xt[lofs[i]];
         }
 #pragma unroll
-        for (int i = 0; i < PUBN; ++i) {
-          if (i < niter) {
-            const int e = e0 + lane + ESTR * i;
-            const size_t o = (size_t)row0 * Din + e + (size_t)ts * xstep;
-            if constexpr (XO) st_granule(S.sout + o, vv[i], tag);
-            else S.dx[o] = vv[i];
+        for (int i = i0; i < i0 + PUBN && i < PUBE; ++i) {
+          if (i < npub) {
+            if constexpr (XO) st_granule(S.sout + o + ESTR * i, vv[i - i0], tag);
+            else S.dx[o + ESTR * i] = vv[i - i0];
           }
         }
       }
