@@ -130,6 +130,15 @@ TORCH_LIBRARY(gnnqc, m) {
         "Tensor bias, Tensor alpha, int act) -> Tensor");
   m.def("gat_node_bwd_input(Tensor x, Tensor bits, Tensor mask, Tensor dout, Tensor W, Tensor a_s, Tensor a_n, "
         "Tensor bias, Tensor alpha, int act) -> Tensor");
+  // fused EdgeConv + node pooling (edge.hip)
+  m.def("edge_adj_bits(Tensor adj, Tensor mask) -> Tensor");
+  m.def("edge_pool_fwd(Tensor x, Tensor bits, Tensor pw, Tensor anom, Tensor W, Tensor bias, Tensor alpha, int act, "
+        "bool mean, int Mp=0, int Cp=0) -> Tensor");
+  m.def("edge_pool_bwd(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor W, Tensor bias, Tensor alpha, int act, "
+        "bool mean, int c_off, bool time_major=False) -> Tensor");
+  m.def("edge_bwd_finalize(Tensor tot, Tensor W, Tensor(a!) dW, Tensor(b!) dbias, Tensor(c!) dalpha) -> ()");
+  m.def("edge_pool_bwd_input(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor W, Tensor bias, Tensor alpha, "
+        "int act, bool mean, int c_off, bool time_major=False) -> Tensor");
   // Conv1D + LeakyReLU (+ GAP) implicit GEMM (conv1d.hip)
   m.def("conv1d_fwd(Tensor x, Tensor W, Tensor b, float alpha, bool gap, bool store_y) -> Tensor[]");
   m.def("conv1d_bwd(Tensor dy, Tensor y, Tensor x, Tensor W, float alpha, bool gap, Tensor(a!) dW, "

@@ -14,7 +14,9 @@ instead of the reference's per-(sample, step) block-diagonal SparseTensor
   chunked over time to bound the ``[B, t, N, N, .]`` edge tensors. The CML classifier
   runs :class:`GATConv` + node pooling through fused HIP kernels instead
   (:func:`gnnqc.ops.gcn.gat_pool`), the network-wide SoilNet classifier per node
-  (:func:`gnnqc.ops.gcn.gat_node_tm`); the layer here is their oracle and fallback.
+  (:func:`gnnqc.ops.gcn.gat_node_tm`); the layer here is their oracle and fallback. The CML
+  classifier likewise runs :class:`EdgeConv` without hidden MLP layers through
+  :func:`gnnqc.ops.gcn.edge_pool`.
 """
 from __future__ import annotations
 
