@@ -139,6 +139,14 @@ TORCH_LIBRARY(gnnqc, m) {
   m.def("edge_bwd_finalize(Tensor tot, Tensor W, Tensor(a!) dW, Tensor(b!) dbias, Tensor(c!) dalpha) -> ()");
   m.def("edge_pool_bwd_input(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor W, Tensor bias, Tensor alpha, "
         "int act, bool mean, int c_off, bool time_major=False) -> Tensor");
+  // fused AGNNConv + node pooling (agnn.hip; the neighbour words are edge_adj_bits')
+  m.def("agnn_pool_fwd(Tensor x, Tensor bits, Tensor pw, Tensor anom, Tensor beta, Tensor alpha, int act, bool mean, "
+        "int Mp=0, int Cp=0) -> Tensor");
+  m.def("agnn_pool_bwd(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor beta, Tensor alpha, int act, bool mean, "
+        "int c_off, bool time_major=False) -> Tensor");
+  m.def("agnn_bwd_finalize(Tensor tot, Tensor(a!) dbeta, Tensor(b!) dalpha) -> ()");
+  m.def("agnn_pool_bwd_input(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor beta, Tensor alpha, int act, "
+        "bool mean, int c_off, bool time_major=False) -> Tensor");
   // Conv1D + LeakyReLU (+ GAP) implicit GEMM (conv1d.hip)
   m.def("conv1d_fwd(Tensor x, Tensor W, Tensor b, float alpha, bool gap, bool store_y) -> Tensor[]");
   m.def("conv1d_bwd(Tensor dy, Tensor y, Tensor x, Tensor W, float alpha, bool gap, Tensor(a!) dW, "

@@ -16,7 +16,9 @@ instead of the reference's per-(sample, step) block-diagonal SparseTensor
   (:func:`gnnqc.ops.gcn.gat_pool`), the network-wide SoilNet classifier per node
   (:func:`gnnqc.ops.gcn.gat_node_tm`); the layer here is their oracle and fallback. The CML
   classifier likewise runs :class:`EdgeConv` without hidden MLP layers through
-  :func:`gnnqc.ops.gcn.edge_pool`.
+  :func:`gnnqc.ops.gcn.edge_pool` and :class:`AGNNConv` through :func:`gnnqc.ops.gcn.agnn_pool`
+  (``agnn.hip``: N <= 64, Cin <= 4, sum or mean aggregation; ``graph_convolution.trainable: false``
+  freezes ``beta``). :class:`GatedGraphConv` and AGNNConv on the network-wide layout stay eager.
 """
 from __future__ import annotations
 
@@ -283,7 +285,9 @@ def make_graph_layer(cfg_gc, in_features: int) -> nn.Module:
         return GeneralConv(in_features, cfg_gc.get("units", 16), cfg_gc.get("dropout_rate", 0.0),
                            cfg_gc.get("aggregation_type", "mean"), act, regularizer=reg)
     if name == "AGNNConv":
-        return AGNNConv(in_features, cfg_gc.get("aggregation_type", "sum"), act)
+        trainable = cfg_gc.get("trainable", True)          # (spektral's default; false freezes beta)
+        return AGNNConv(in_features, cfg_gc.get("aggregation_type", "sum"), act,
+                        trainable=True if trainable is None else bool(trainable))
     if name == "GATConv":
         return GATConv(in_features, cfg_gc.get("units", 16), cfg_gc.get("attention_heads") or 1,
                        dropout_rate=cfg_gc.get("dropout_rate", 0.5), activation=act, regularizer=reg)

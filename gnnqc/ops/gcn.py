@@ -655,6 +655,111 @@ def edge_pool(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_m
 
 
 # ---------------------------------------------------------------------------------------------
+# AGNNConv + node pooling + concat (agnn.hip). ``layer`` is a :class:`gnnqc.models.graphconv.AGNNConv`
+# (or anything with its attributes); the eager path is the layer itself plus :func:`pool_nodes`.
+AGNN_MAX_NODES = 64                     # agnn.hip: one 64-bit neighbour word per node
+
+
+class _HipAGNNPool(torch.autograd.Function):
+    """Fused cosine-attention softmax -> neighbour aggregate -> activation -> node pool -> concat
+    (HIP). Launches: edge_adj_bits and agnn_pool_fwd forward; agnn_pool_bwd, its fixed-order record
+    sum and agnn_bwd_finalize (+ agnn_pool_bwd_input when dx is needed) backward. Parameter gradients
+    go straight into the optimiser's flat buffer under direct accumulation, like :class:`_HipEdgePool`'s.
+    With no parameter needing a gradient (a frozen ``beta`` and no PReLU) agnn_pool_bwd is not launched."""
+
+    @staticmethod
+    def forward(ctx, x, adj, mask, anom, pw, beta, alpha, act: int, mean: bool, Mp: int = 0, Cp: int = 0):
+        from ..utils.native import hip_ops
+        ops = hip_ops()
+        bits = ops.edge_adj_bits(adj, mask)
+        empty = x.new_zeros(0)
+        anom_t = anom.contiguous() if anom is not None else empty
+        al = alpha.contiguous() if alpha is not None else empty
+        out = ops.agnn_pool_fwd(x, bits, pw, anom_t, beta.contiguous(), al, int(act), bool(mean), int(Mp), int(Cp))
+        ctx.tm = Mp > 0
+        ctx.act, ctx.mean = int(act), bool(mean)
+        ctx.ca = 0 if anom is None else anom.shape[-1]
+        ctx.has_anom = anom is not None
+        ctx.params = (beta, alpha)
+        ctx.save_for_backward(x, bits, pw, beta, al)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from ..utils.native import hip_ops
+        from .wgrad import _grad_sink
+        ops = hip_ops()
+        x, bits, pw, beta, al = ctx.saved_tensors
+        dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        need_p = list(need[5:7])
+        args = (beta.contiguous(), al, ctx.act, ctx.mean, ctx.ca, ctx.tm)
+        empty = x.new_zeros(0)
+        grads = [None] * 2
+        if any(need_p):
+            tot = ops.agnn_pool_bwd(x, bits, pw, dout, *args)
+            # (a parameter that needs no gradient gets an empty sink: the finalizer discards its sum)
+            sinks = [(_grad_sink(p) if n else (empty, True)) for p, n in zip(ctx.params, need_p)]
+            ops.agnn_bwd_finalize(tot, *[s[0] for s in sinks])
+            grads = [None if direct or not n else buf for (buf, direct), n in zip(sinks, need_p)]
+        dx = ops.agnn_pool_bwd_input(x, bits, pw, dout, *args) if need[0] else None
+        danom = None
+        if ctx.has_anom and need[3]:
+            danom = dout[:, : x.shape[0], : ctx.ca].transpose(0, 1) if ctx.tm else dout[..., : ctx.ca]
+        return (dx, None, None, danom, None, *grads, None, None, None, None)
+
+
+def agnn_pool_hip_ok(x: torch.Tensor, layer, pooling: str) -> bool:
+    """Whether :func:`agnn_pool` runs the HIP kernels: a float32 GPU tensor ``[B, T, N, Cin]`` with
+    1 <= N <= 64 and 1 <= Cin <= 4, a layer built for that width, sum or mean aggregation, linear node
+    pooling and an activation the kernels implement. ``GNNQC_AGNN_HIP=0`` keeps the eager layer
+    (A/B runs)."""
+    import os
+
+    from . import use_hip
+    if os.environ.get("GNNQC_AGNN_HIP", "1") != "1" or x.dim() != 4 or x.dtype != torch.float32:
+        return False
+    return bool(use_hip(x) and 1 <= x.shape[2] <= AGNN_MAX_NODES and 1 <= x.shape[-1] <= 4
+                and layer.in_features == x.shape[-1]
+                and layer.aggregate in ("sum", "mean") and pooling in ("mean", "sum", "selection")
+                and layer.activation in _GAT_ACT)
+
+
+def agnn_pool_eager(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_major: bool = False):
+    """Eager oracle of :func:`agnn_pool` in its output layouts: the layer, :func:`pool_nodes` and
+    ``Concatenate([anom, pooled])``."""
+    pooled = pool_nodes(layer(x, adj, mask), mask, anom_pos, pooling)
+    out = pooled if anom is None else torch.cat([anom, pooled], dim=-1)
+    return (_time_major_pad(out), x.shape[0]) if time_major else out
+
+
+def agnn_pool(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_major: bool = False):
+    """AGNNConv + node pooling + concat -> LSTM input ``[B, T, Ca + Cin]``; mirrors :func:`edge_pool`.
+
+    Uses the fused HIP kernels when :func:`agnn_pool_hip_ok`, otherwise the eager layer plus
+    :func:`pool_nodes`. The kernels take ``adj`` as the 0/1 matrix of the data pipeline (an entry > 0
+    is an edge; under ``aggregate: mean`` the degree is the number of such entries).
+    ``time_major=True`` (HIP path only) returns ``(h [T, Mp, Cp], B)``, the time-major, row- and
+    channel-padded input of :meth:`gnnqc.models.timelayer.TimeLayer.forward_time_major`, written by
+    the kernel itself."""
+    if agnn_pool_hip_ok(x, layer, pooling):
+        B = x.shape[0]
+        Mp = Cp = 0
+        if time_major:
+            Mp = (B + 15) // 16 * 16
+            Cp = layer.out_features + (anom.shape[-1] if anom is not None else 0)
+            Cp += (-Cp) % 4
+        mask_f = mask.float().contiguous()
+        pw = gat_pool_weights(mask_f, anom_pos.long() if anom_pos is not None else None, pooling)
+        out = _HipAGNNPool.apply(x.contiguous(), adj.float().contiguous(), mask_f, anom, pw, layer.beta,
+                                 layer.prelu_alpha, _GAT_ACT[layer.activation], layer.aggregate == "mean", Mp, Cp)
+        return (out, B) if time_major else out
+    if time_major:
+        raise ValueError("agnn_pool(time_major=True) needs the HIP path")
+    return agnn_pool_eager(x, adj, mask, anom, anom_pos, layer, pooling)
+
+
+# ---------------------------------------------------------------------------------------------
 # GATConv per node -> time-major LSTM input (gat_node.hip): the network-wide SoilNet front end.
 GAT_NODE_MAX_NODES = 256                # gat_node.hip: up to four 64-bit neighbour mask words per node
 
@@ -755,5 +860,6 @@ def gat_node_tm_eager(x, adj, mask, layer, cpad_to: int = 4):
 __all__ = ["gat_pool", "gat_pool_eager", "gat_pool_hip_ok", "gat_pool_weights",
            "gat_node_tm", "gat_node_tm_eager", "gat_node_tm_ok",
            "edge_pool", "edge_pool_eager", "edge_pool_hip_ok",
+           "agnn_pool", "agnn_pool_eager", "agnn_pool_hip_ok",
            "gcn_pool", "gcn_pool_hip_ok", "gcn_node_tm", "gcn_node_tm_eager", "gcn_node_tm_ok", "node_pool_weights", "masked_batchnorm", "general_conv_eager", "pool_nodes",
            "normalized_adjacency", "prelu"]
