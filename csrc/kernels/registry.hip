@@ -147,6 +147,15 @@ TORCH_LIBRARY(gnnqc, m) {
   m.def("agnn_bwd_finalize(Tensor tot, Tensor(a!) dbeta, Tensor(b!) dalpha) -> ()");
   m.def("agnn_pool_bwd_input(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor beta, Tensor alpha, int act, "
         "bool mean, int c_off, bool time_major=False) -> Tensor");
+  // fused GatedGraphConv + node pooling (gated.hip; the neighbour words are edge_adj_bits')
+  m.def("gated_pool_fwd(Tensor x, Tensor bits, Tensor pw, Tensor anom, Tensor Wl, Tensor K, Tensor R, Tensor bias, "
+        "Tensor alpha, int act, int Mp=0, int Cp=0) -> Tensor");
+  m.def("gated_pool_bwd(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor Wl, Tensor K, Tensor R, Tensor bias, "
+        "Tensor alpha, int act, int c_off, bool time_major=False) -> Tensor");
+  m.def("gated_bwd_finalize(Tensor tot, int L, int C, Tensor(a!) dW, Tensor(b!) dK, Tensor(c!) dR, Tensor(d!) dbias, "
+        "Tensor(e!) dalpha) -> ()");
+  m.def("gated_pool_bwd_input(Tensor x, Tensor bits, Tensor pw, Tensor dout, Tensor Wl, Tensor K, Tensor R, "
+        "Tensor bias, Tensor alpha, int act, int c_off, bool time_major=False) -> Tensor");
   // Conv1D + LeakyReLU (+ GAP) implicit GEMM (conv1d.hip)
   m.def("conv1d_fwd(Tensor x, Tensor W, Tensor b, float alpha, bool gap, bool store_y) -> Tensor[]");
   m.def("conv1d_bwd(Tensor dy, Tensor y, Tensor x, Tensor W, float alpha, bool gap, Tensor(a!) dW, "

@@ -26,9 +26,9 @@ import torch.nn as nn
 
 from ..config import freq_minutes
 from ..ops.gcn import (agnn_pool, agnn_pool_hip_ok, edge_pool, edge_pool_hip_ok, gat_node_tm, gat_node_tm_ok, gat_pool,
-                       gat_pool_hip_ok, gcn_node_tm, gcn_node_tm_ok, gcn_pool, gcn_pool_from_store, gcn_pool_hip_ok,
-                       pool_nodes, store_gcn_ok)
-from .graphconv import AGNNConv, EdgeConv, GATConv, GeneralConv, make_graph_layer
+                       gat_pool_hip_ok, gated_pool, gated_pool_hip_ok, gcn_node_tm, gcn_node_tm_ok, gcn_pool,
+                       gcn_pool_from_store, gcn_pool_hip_ok, pool_nodes, store_gcn_ok)
+from .graphconv import AGNNConv, EdgeConv, GATConv, GatedGraphConv, GeneralConv, make_graph_layer
 from .layers import Dense, Dropout, LeakyReLU
 from .spatial import SensorsTimeLayer, SpatialTransformer
 from .timelayer import TimeLayer
@@ -156,6 +156,9 @@ class GCNClassifier(nn.Module):
             if isinstance(self.gcn_layer, AGNNConv):
                 # (fused HIP kernels when agnn_pool_hip_ok, else the eager layer + pool_nodes + cat)
                 return agnn_pool(feats, adj, mask, anom, anom_pos, self.gcn_layer, pooling)
+            if isinstance(self.gcn_layer, GatedGraphConv):
+                # (fused HIP kernels when gated_pool_hip_ok, else the eager layer + pool_nodes + cat)
+                return gated_pool(feats, adj, mask, anom, anom_pos, self.gcn_layer, pooling)
             h = self.gcn_layer(feats, adj, mask)
             return torch.cat([anom, pool_nodes(h, mask, anom_pos, pooling)], -1)
         x, adj, mask = inputs[:3]
@@ -252,6 +255,24 @@ class GCNClassifier(nn.Module):
         pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
         return agnn_pool(x, adj, mask, anom, anom_pos, self.gcn_layer, pooling, time_major=True)
 
+    def _cml_gated_time_major(self, inputs) -> bool:
+        """CML GatedGraphConv fast path: the fused message-round + pooling kernel writes the time-major
+        LSTM input."""
+        if (not self.per_sensor or not isinstance(self.gcn_layer, GatedGraphConv)
+                or self.sensors_time_layer is not None):
+            return False
+        if self.spatial_transformer is not None or len(inputs) > 5:
+            return False
+        x, anom = inputs[0], inputs[1]
+        pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
+        return (gated_pool_hip_ok(x, self.gcn_layer, pooling)
+                and self.time_layer.time_major_ok(x, self.gcn_layer.out_features + anom.shape[-1]))
+
+    def _gated_time_major_input(self, inputs):
+        x, anom, adj, mask, anom_pos = inputs[:5]
+        pooling = "selection" if self.pooling_type == "selection" else self.aggregation_type
+        return gated_pool(x, adj, mask, anom, anom_pos, self.gcn_layer, pooling, time_major=True)
+
     def features(self, inputs) -> torch.Tensor:
         """TimeLayer output rows [R, F] (CML: R = B; SoilNet: R = B*N) - the head's input."""
         if self._cml_gat_time_major(inputs):
@@ -260,6 +281,8 @@ class GCNClassifier(nn.Module):
             return self.time_layer.forward_time_major(*self._edge_time_major_input(inputs))
         if self._cml_agnn_time_major(inputs):
             return self.time_layer.forward_time_major(*self._agnn_time_major_input(inputs))
+        if self._cml_gated_time_major(inputs):
+            return self.time_layer.forward_time_major(*self._gated_time_major_input(inputs))
         if self._cml_time_major(inputs):
             x, anom, adj, mask, anom_pos = inputs[:5]
             g = self.gcn_layer
@@ -297,7 +320,9 @@ class GCNClassifier(nn.Module):
         gat = self._cml_gat_time_major(inputs)
         edge = self._cml_edge_time_major(inputs)
         agnn = self._cml_agnn_time_major(inputs)
-        if spec is None or not self.per_sensor or not (gat or edge or agnn or self._cml_time_major(inputs)):
+        gated = self._cml_gated_time_major(inputs)
+        if spec is None or not self.per_sensor or not (gat or edge or agnn or gated
+                                                       or self._cml_time_major(inputs)):
             return None
         if any(d.kernel.shape[1] != 64 for d in spec[:2]) or spec[2].kernel.shape != (64, 1):
             return None
@@ -309,6 +334,8 @@ class GCNClassifier(nn.Module):
             h, M = self._edge_time_major_input(inputs)
         elif agnn:
             h, M = self._agnn_time_major_input(inputs)
+        elif gated:
+            h, M = self._gated_time_major_input(inputs)
         else:
             x, anom, adj, mask_n, anom_pos = inputs[:5]
             g = self.gcn_layer

@@ -18,7 +18,9 @@ instead of the reference's per-(sample, step) block-diagonal SparseTensor
   classifier likewise runs :class:`EdgeConv` without hidden MLP layers through
   :func:`gnnqc.ops.gcn.edge_pool` and :class:`AGNNConv` through :func:`gnnqc.ops.gcn.agnn_pool`
   (``agnn.hip``: N <= 64, Cin <= 4, sum or mean aggregation; ``graph_convolution.trainable: false``
-  freezes ``beta``). :class:`GatedGraphConv` and AGNNConv on the network-wide layout stay eager.
+  freezes ``beta``) and :class:`GatedGraphConv` through :func:`gnnqc.ops.gcn.gated_pool`
+  (``gated.hip``: N <= 64, Cin <= 4, ``units`` in {8, 16, 32}, 1..4 ``n_layers``). On the network-wide
+  layout AGNNConv, EdgeConv and GatedGraphConv stay eager.
 """
 from __future__ import annotations
 

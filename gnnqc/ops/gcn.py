@@ -760,6 +760,117 @@ def agnn_pool(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_m
 
 
 # ---------------------------------------------------------------------------------------------
+# GatedGraphConv + node pooling + concat (gated.hip). ``layer`` is a
+# :class:`gnnqc.models.graphconv.GatedGraphConv` (or anything with its attributes); the eager path is
+# the layer itself plus :func:`pool_nodes`.
+GATED_MAX_NODES = 64                    # gated.hip: one 64-bit neighbour word per node
+GATED_WIDTHS = (8, 16, 32)              # gated.hip GQ_GATED_DISPATCH: channels
+GATED_MAX_LAYERS = 4                    # gated.hip: dW_l accumulators of the backward
+
+
+class _HipGatedPool(torch.autograd.Function):
+    """Fused message rounds (``h W_l`` -> neighbour sum -> GRU cell) -> activation -> node pool ->
+    concat (HIP). Launches: edge_adj_bits and gated_pool_fwd forward; gated_pool_bwd, its fixed-order
+    record sum and gated_bwd_finalize (+ gated_pool_bwd_input when dx is needed) backward. Parameter
+    gradients go straight into the optimiser's flat buffer under direct accumulation, like
+    :class:`_HipAGNNPool`'s. With no parameter needing a gradient gated_pool_bwd is not launched."""
+
+    @staticmethod
+    def forward(ctx, x, adj, mask, anom, pw, Wl, K, R, bias, alpha, act: int, Mp: int = 0, Cp: int = 0):
+        from ..utils.native import hip_ops
+        ops = hip_ops()
+        bits = ops.edge_adj_bits(adj, mask)
+        empty = x.new_zeros(0)
+        anom_t = anom.contiguous() if anom is not None else empty
+        al = alpha.contiguous() if alpha is not None else empty
+        out = ops.gated_pool_fwd(x, bits, pw, anom_t, Wl.contiguous(), K.contiguous(), R.contiguous(),
+                                 bias.contiguous(), al, int(act), int(Mp), int(Cp))
+        ctx.tm = Mp > 0
+        ctx.act = int(act)
+        ctx.ca = 0 if anom is None else anom.shape[-1]
+        ctx.has_anom = anom is not None
+        ctx.params = (Wl, K, R, bias, alpha)
+        ctx.save_for_backward(x, bits, pw, Wl, K, R, bias, al)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from ..utils.native import hip_ops
+        from .wgrad import _grad_sink
+        ops = hip_ops()
+        x, bits, pw, Wl, K, R, bias, al = ctx.saved_tensors
+        dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        need_p = list(need[5:10])
+        args = (Wl.contiguous(), K.contiguous(), R.contiguous(), bias.contiguous(), al, ctx.act, ctx.ca, ctx.tm)
+        empty = x.new_zeros(0)
+        grads = [None] * 5
+        if any(need_p):
+            tot = ops.gated_pool_bwd(x, bits, pw, dout, *args)
+            # (a parameter that needs no gradient gets an empty sink: the finalizer discards its sum)
+            sinks = [(_grad_sink(p) if n else (empty, True)) for p, n in zip(ctx.params, need_p)]
+            ops.gated_bwd_finalize(tot, int(Wl.shape[0]), int(Wl.shape[1]), *[s[0] for s in sinks])
+            grads = [None if direct or not n else buf for (buf, direct), n in zip(sinks, need_p)]
+        dx = ops.gated_pool_bwd_input(x, bits, pw, dout, *args) if need[0] else None
+        danom = None
+        if ctx.has_anom and need[3]:
+            danom = dout[:, : x.shape[0], : ctx.ca].transpose(0, 1) if ctx.tm else dout[..., : ctx.ca]
+        return (dx, None, None, danom, None, *grads, None, None, None)
+
+
+def gated_pool_hip_ok(x: torch.Tensor, layer, pooling: str) -> bool:
+    """Whether :func:`gated_pool` runs the HIP kernels: a float32 GPU tensor ``[B, T, N, Cin]`` with
+    1 <= N <= 64 and 1 <= Cin <= 4, a layer built for that input width with an instantiated channel
+    count and 1..4 message rounds, linear node pooling and an activation the kernels implement.
+    ``GNNQC_GATED_HIP=0`` keeps the eager layer (A/B runs)."""
+    import os
+
+    from . import use_hip
+    if os.environ.get("GNNQC_GATED_HIP", "1") != "1" or x.dim() != 4 or x.dtype != torch.float32:
+        return False
+    C = layer.channels
+    return bool(use_hip(x) and 1 <= x.shape[2] <= GATED_MAX_NODES and 1 <= x.shape[-1] <= 4
+                and layer.in_features == x.shape[-1] and x.shape[-1] <= C and C in GATED_WIDTHS
+                and 1 <= layer.n_layers <= GATED_MAX_LAYERS and tuple(layer.kernel.shape) == (layer.n_layers, C, C)
+                and pooling in ("mean", "sum", "selection") and layer.activation in _GAT_ACT)
+
+
+def gated_pool_eager(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_major: bool = False):
+    """Eager oracle of :func:`gated_pool` in its output layouts: the layer, :func:`pool_nodes` and
+    ``Concatenate([anom, pooled])``."""
+    pooled = pool_nodes(layer(x, adj, mask), mask, anom_pos, pooling)
+    out = pooled if anom is None else torch.cat([anom, pooled], dim=-1)
+    return (_time_major_pad(out), x.shape[0]) if time_major else out
+
+
+def gated_pool(x, adj, mask, anom, anom_pos, layer, pooling: str = "mean", time_major: bool = False):
+    """GatedGraphConv + node pooling + concat -> LSTM input ``[B, T, Ca + C]``; mirrors :func:`agnn_pool`.
+
+    Uses the fused HIP kernels when :func:`gated_pool_hip_ok`, otherwise the eager layer plus
+    :func:`pool_nodes`. The kernels take ``adj`` as the 0/1 matrix of the data pipeline (an entry > 0
+    is an edge of weight one; a weighted adjacency is not supported and not checked).
+    ``time_major=True`` (HIP path only) returns ``(h [T, Mp, Cp], B)``, the time-major, row- and
+    channel-padded input of :meth:`gnnqc.models.timelayer.TimeLayer.forward_time_major`, written by
+    the kernel itself."""
+    if gated_pool_hip_ok(x, layer, pooling):
+        B = x.shape[0]
+        Mp = Cp = 0
+        if time_major:
+            Mp = (B + 15) // 16 * 16
+            Cp = layer.out_features + (anom.shape[-1] if anom is not None else 0)
+            Cp += (-Cp) % 4
+        mask_f = mask.float().contiguous()
+        pw = gat_pool_weights(mask_f, anom_pos.long() if anom_pos is not None else None, pooling)
+        out = _HipGatedPool.apply(x.contiguous(), adj.float().contiguous(), mask_f, anom, pw, layer.kernel,
+                                  layer.rnn.kernel, layer.rnn.recurrent_kernel, layer.rnn.bias, layer.prelu_alpha,
+                                  _GAT_ACT[layer.activation], Mp, Cp)
+        return (out, B) if time_major else out
+    if time_major:
+        raise ValueError("gated_pool(time_major=True) needs the HIP path")
+    return gated_pool_eager(x, adj, mask, anom, anom_pos, layer, pooling)
+
+
+# ---------------------------------------------------------------------------------------------
 # GATConv per node -> time-major LSTM input (gat_node.hip): the network-wide SoilNet front end.
 GAT_NODE_MAX_NODES = 256                # gat_node.hip: up to four 64-bit neighbour mask words per node
 
@@ -861,5 +972,6 @@ __all__ = ["gat_pool", "gat_pool_eager", "gat_pool_hip_ok", "gat_pool_weights",
            "gat_node_tm", "gat_node_tm_eager", "gat_node_tm_ok",
            "edge_pool", "edge_pool_eager", "edge_pool_hip_ok",
            "agnn_pool", "agnn_pool_eager", "agnn_pool_hip_ok",
+           "gated_pool", "gated_pool_eager", "gated_pool_hip_ok",
            "gcn_pool", "gcn_pool_hip_ok", "gcn_node_tm", "gcn_node_tm_eager", "gcn_node_tm_ok", "node_pool_weights", "masked_batchnorm", "general_conv_eager", "pool_nodes",
            "normalized_adjacency", "prelu"]
